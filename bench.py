@@ -18,16 +18,24 @@ first-fail vector after the last step.  `--workload c2|c3` runs the per-GPU
 
 Multi-GPU (one rank per GPU): `--gpus N` under torch.distributed.run, or
 `--gpus N` alone, which starts torch.distributed.run itself as a child
-process before anything touches the GPU.  With a process group the line
-also carries `scatter_gather`: the same C4 job with the whole arrays held by
+process before anything touches the GPU.  With a process group and `--full`
+the line also carries `scatter_gather`: the same C4 job with the whole arrays held by
 rank 0, scattered and gathered every step by one grouped RCCL send/recv
 batch per direction over xGMI (SURVEY.md 8e's second curve).
 
 Prints ONE JSON line (rank 0).  Per-kernel HIP-event timings on the launch
 stream (--samples launches of each kernel, spread over the timed steps) feed
-`roofline`; `cpu_baseline` times the C oracle (a multithreaded port of the
-reference's BigInteger algorithm) on a bounded sample, on rank 0 at every
-world size, after all GPU work and the process group are done.
+`roofline`.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs when `--dump-outputs DIR` is given and prints the line.  `--full`
+adds everything beside the headline figure, after the timed steps: the
+same-pattern stream probe, the checks of the outputs themselves, the
+`host_memory` and `scatter_gather` phases, and `cpu_baseline`, which times
+the C oracle (a multithreaded port of the reference's BigInteger algorithm)
+on a bounded sample, on rank 0 at every world size, after all GPU work and
+the process group are done.  Without `--full` those sub-objects say
+`skipped` and `verified` stands for the per-step MAC verdicts alone.
 """
 from __future__ import annotations
 
@@ -128,6 +136,17 @@ def parse():
     # steps take ~80 ms; host and scatter modes move GBs per step: 5 after 1
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="device mode: after the timed steps also run everything beside the headline "
+                         "figure -- the same-pattern stream probe, the output checks, the host_memory "
+                         "and scatter/gather phases and the CPU baseline (each still has its own "
+                         "--no-... switch); without it the line carries them as skipped")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="device mode: after the timed steps write what the last timed step computed "
+                         "to DIR/<name>.npy (float64): `masked` (K_MASK's words) and `secrets` (K_RV's "
+                         "canonical secrets) as rows of four 32-bit limbs, least significant first, "
+                         "for a fixed seeded sample of at most 2^18 words (`sample_index`), and "
+                         "`first_fail`, the step's two verify verdicts (-1 = no MAC failure)")
     ap.add_argument("--workload", choices=["auto", "c2", "c3", "c4"], default="auto",
                     help="device mode: BASELINE config; auto = C4 (2^26 words in total, 2 parties, "
                          "split over the ranks) at every world size; c2 / c3 are per-GPU "
@@ -1143,6 +1162,37 @@ def workload_config(a, world):
             "words_total": W * world, "words_per_gpu": W, "parties": n, "parallelism": "dp%d" % world}
 
 
+DUMP_SAMPLE_WORDS = 1 << 18  # 2 arrays x 2^18 words x 4 limbs x 8 B = 16 MiB of .npy
+
+
+def dump_outputs(torch, outdir, masked, ys, last_verdicts, rank, world):
+    """--dump-outputs: the arrays the last timed step handed back, as float64
+    .npy files (a 32-bit limb is exact in a double).  The word sample is
+    fixed by its seed and the shard size alone, so two builds given the same
+    arguments write the same rows.  With several ranks every rank writes its
+    own shard's sample (`<name>_rank<r>.npy`)."""
+    import numpy as np
+    W = masked.shape[0]
+    if W <= DUMP_SAMPLE_WORDS:
+        idx = np.arange(W, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(20240607).integers(0, W, DUMP_SAMPLE_WORDS))
+    sel = torch.from_numpy(idx).cuda()
+    os.makedirs(outdir, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+
+    def limbs(t):  # (W, 16) little-endian bytes -> (S, 4) 32-bit limbs as float64
+        return t[sel].cpu().numpy().view("<u4").astype(np.float64)
+
+    ff = last_verdicts.cpu().numpy().astype(np.int64)
+    arrays = {"masked": limbs(masked), "secrets": limbs(ys),
+              "first_fail": np.where(ff == NO_FAIL, -1, ff).astype(np.float64),
+              "sample_index": idx.astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, "%s%s.npy" % (name, tag)), arr)
+    return {"dir": outdir, "arrays": {k + tag: list(v.shape) for k, v in arrays.items()}, "dtype": "float64"}
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1303,23 +1353,30 @@ def main():
         t_mask = max(r["k_mask_ms"] for r in ranks)
         t_rv = max(r["k_rv_ms"] for r in ranks)
     ok = bool((verdicts == NO_FAIL).all().item())
-    # After the timed region: the same access pattern as K_MASK with no
-    # arithmetic (amph_stream_probe), stamped the same way -- what this
-    # pattern achieves at this size on this GPU, beside the 8 TB/s spec peak.
-    scratch_ff = torch.full((1,), NO_FAIL, dtype=torch.int64, device="cuda")
-    ys2 = torch.empty_like(ys)
+    dumped = None
+    if a.dump_outputs:  # the last timed step's outputs, before anything else touches the device
+        dumped = dump_outputs(torch, a.dump_outputs, masked, ys, verdicts[total - 1], rank, world)
+    probe_ms = None
+    checks = {}
+    if a.full:
+        # After the timed region: the same access pattern as K_MASK with no
+        # arithmetic (amph_stream_probe), stamped the same way -- what this
+        # pattern achieves at this size on this GPU, beside the 8 TB/s spec peak.
+        scratch_ff = torch.full((1,), NO_FAIL, dtype=torch.int64, device="cuda")
+        ys2 = torch.empty_like(ys)
 
-    def k_rv_launch():  # the launch that precedes every K_MASK in the timed steps
-        assert lib.lib.amph_recombine_verify(
-            ctx._h, share_arr, n, ys2.data_ptr(),
-            C.cast(C.c_void_p(scratch_ff.data_ptr()), C.POINTER(C.c_int64)), flags, stream) == 0
+        def k_rv_launch():  # the launch that precedes every K_MASK in the timed steps
+            assert lib.lib.amph_recombine_verify(
+                ctx._h, share_arr, n, ys2.data_ptr(),
+                C.cast(C.c_void_p(scratch_ff.data_ptr()), C.POINTER(C.c_int64)), flags, stream) == 0
 
-    probe_ms = stream_probe_ms(lib, C, ctx, mask_arr, n, secrets, W, stream, ns, k_rv_launch)
-    # After the timed region: the outputs themselves are checked, not only the
-    # absence of a MAC failure (a kernel that flags nothing and writes wrong
-    # words must not report verified).
-    checks = check_outputs(ctx, lib, torch, C, stream, flags, n, W, secrets, masked, ys, mplain, splain,
-                           share_arr, share_odos, TEST_PRIME)
+        probe_ms = stream_probe_ms(lib, C, ctx, mask_arr, n, secrets, W, stream, ns, k_rv_launch)
+        del ys2
+        # After the timed region: the outputs themselves are checked, not only
+        # the absence of a MAC failure (a kernel that flags nothing and writes
+        # wrong words must not report verified).
+        checks = check_outputs(ctx, lib, torch, C, stream, flags, n, W, secrets, masked, ys, mplain, splain,
+                               share_arr, share_odos, TEST_PRIME)
     checks["honest_verdicts"] = ok
     if distributed:
         cv = torch.tensor([int(all(checks.values()))], dtype=torch.int64, device="cuda")
@@ -1370,7 +1427,9 @@ def main():
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "bytes_per_word": bpw, "traffic": traffic},
-            "pattern_probe": pattern_probe(probe_ms, n, W, kern),
+            "pattern_probe": pattern_probe(probe_ms, n, W, kern) if probe_ms else {"skipped": "needs --full"},
+            "full": a.full,
+            "dumped_outputs": dumped,
             "per_rank": ranks,
             "ranks_summary": ranks_summary(ranks, dist.get_world_size() if distributed else 1),
             "host_memory": None,
@@ -1380,20 +1439,21 @@ def main():
     # The root-held C4 rate (RCCL scatter/gather over xGMI) in the same run,
     # once the device-resident arrays are gone.
     resident = total_words * a.steps / el
-    del mask_odos, mbuf, mplain, share_odos, sbuf, splain, secrets, masked, ys, ys2
+    del mask_odos, mbuf, mplain, share_odos, sbuf, splain, secrets, masked, ys
     del mviews, sviews, mask_arr, share_arr
-    torch.cuda.empty_cache()
+    if a.full:
+        torch.cuda.empty_cache()
     # The PCIe-inclusive rate (C5's per-GPU share from page-locked host
     # memory), before the scatter/gather phase: nothing it measures depends
     # on a point-to-point exchange.
     hm = None
-    if not a.no_host_phase:
+    if a.full and not a.no_host_phase:
         hm = host_memory_phase(a, torch, dist, ctx, rank, world, distributed)
         if rank == 0 and hm and "verified" in hm:
             ok = ok and hm["verified"]
     host_aborted = bool(hm and hm.get("aborted"))
     sg = None
-    if distributed and a.scaling == "strong" and not a.no_scatter_gather and not host_aborted:
+    if a.full and distributed and a.scaling == "strong" and not a.no_scatter_gather and not host_aborted:
         sg = scatter_gather_phase(a, A, torch, dist, ctx, rank, world, resident)
         if rank == 0 and sg and "verified" in sg:
             ok = ok and sg["verified"]
@@ -1410,12 +1470,16 @@ def main():
     if rank == 0:
         line["verified"] = ok
         line["host_memory"] = hm if not a.no_host_phase else {"skipped": "--no-host-phase"}
+        if not a.full:
+            line["host_memory"] = line["cpu_baseline"] = {"skipped": "needs --full"}
         if aborted and sg is not None and "aborted" not in sg:
             sg = dict(sg, aborted_after=True)
         if sg is not None:
             line["scatter_gather"] = sg
         elif host_aborted and a.scaling == "strong" and not a.no_scatter_gather and distributed:
             line["scatter_gather"] = {"skipped": "not run: the host_memory phase aborted the process group"}
+        elif not a.full:
+            line["scatter_gather"] = {"skipped": "needs --full"}
         elif a.scaling == "strong" and not a.no_scatter_gather:
             line["scatter_gather"] = {"skipped": "world size 1: the root's arrays are the only shard, "
                                                  "nothing crosses a link (device-resident value = "
@@ -1428,7 +1492,7 @@ def main():
             partial = ["process group aborted after the phases"]
         line["partial"] = partial or None
         # the CPU baseline on rank 0 at EVERY world size, after the GPU work
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(n, a.cpu_seconds)
         emit(line)
     if aborted:

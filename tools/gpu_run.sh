@@ -8,9 +8,9 @@
 # kinds:
 #   smoke                        __graft_entry__.smoke()
 #   tests [pytest args]          default: the whole -m gpu suite
-#   bench [bench.py args]        one JSON line -> <n>_bench.json
-#   stats [bench.py args]        rocprofv3 --kernel-trace --stats of bench.py
-#   pmc COUNTERS [bench args]    one rocprofv3 --pmc pass of bench.py (--kernel-trace only beside it)
+#   bench [bench.py args]        bench.py --full: one JSON line -> <n>_bench.json
+#   stats [bench.py args]        rocprofv3 --kernel-trace --stats of bench.py --full
+#   pmc COUNTERS [bench args]    one rocprofv3 --pmc pass of bench.py --full (--kernel-trace only beside it)
 #   py LIMIT SCRIPT [args]       python -u SCRIPT args
 #   statspy SCRIPT [args]        rocprofv3 --kernel-trace --stats of a python script
 #   pmcpy COUNTERS SCRIPT [args] one --pmc pass of a python script
@@ -31,12 +31,12 @@ run_step() {
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$base.log" 2>&1 ;;
     tests) if [ $# -eq 0 ]; then set -- -m gpu tests; fi
            timeout -k 10 1500 python -u -m pytest -x -v --timeout 120 --timeout-method thread "$@" > "$base.log" 2>&1 ;;
-    bench) timeout -k 10 600 python -u bench.py "$@" > "$base.json" 2> "$base.err" ;;
+    bench) timeout -k 10 600 python -u bench.py --full "$@" > "$base.json" 2> "$base.err" ;;
     stats) timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$base" -o kt --output-format csv -- \
-             python3 "$ROOT/bench.py" --no-cpu-baseline "$@" > "$base.log" 2>&1 ;;
+             python3 "$ROOT/bench.py" --full --no-cpu-baseline "$@" > "$base.log" 2>&1 ;;
     pmc) local c=$1; shift
          timeout -s KILL 150 rocprofv3 --kernel-trace --pmc $c -d "$base" -o pmc --output-format csv -- \
-           python3 "$ROOT/bench.py" --no-cpu-baseline "$@" > "$base.log" 2>&1 ;;
+           python3 "$ROOT/bench.py" --full --no-cpu-baseline "$@" > "$base.log" 2>&1 ;;
     py) local lim=$1; shift
         timeout -k 10 "$lim" python -u "$@" > "$base.log" 2>&1 ;;
     statspy) timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$base" -o kt --output-format csv -- \
