@@ -106,6 +106,10 @@ def _load():
     L.amph_stream_probe.argtypes = [vp, vp, i32, vp, sz, vp, vp]
     L.amph_recombine_verify_b64.argtypes = [vp, vp, i32, sz, vp, i64p, i64p, u32, vp]
     L.amph_mask_input_b64.argtypes = [vp, vp, i32, sz, vp, sz, vp, vp, i64p, i64p, u32, vp]
+    L.amph_masked_input_data_chars.restype = sz
+    L.amph_masked_input_data_chars.argtypes = [sz]
+    L.amph_convert_share_json.argtypes = [vp, vp, sz, sz, vp, C.c_char_p, i32, vp, i64p, u32, vp]
+    L.amph_mask_input_json.argtypes = [vp, vp, i32, sz, vp, sz, vp, sz, i64p, i64p, u32, vp]
     L.amph_party_begin.argtypes = [vp, vp, sz, vp, vp, sz, i32, vp, vp, vp, C.POINTER(vp)]
     L.amph_party_words.restype = sz
     L.amph_party_words.argtypes = [vp]
@@ -164,7 +168,8 @@ EXPORTED = ["amph_ctx_create", "amph_ctx_create_multi", "amph_ctx_device_count",
             "amph_timing_event_elapsed_ms", "amph_base64_encode", "amph_base64_decode",
             "amph_base64_encode_words", "amph_base64_decode_words", "amph_exchange_max_chars",
             "amph_exchange_encode", "amph_exchange_decode", "amph_stream_probe",
-            "amph_recombine_verify_b64", "amph_mask_input_b64", "amph_party_begin", "amph_party_words", "amph_party_text_len",
+            "amph_recombine_verify_b64", "amph_mask_input_b64", "amph_masked_input_data_chars",
+            "amph_convert_share_json", "amph_mask_input_json", "amph_party_begin", "amph_party_words", "amph_party_text_len",
             "amph_party_text", "amph_party_partner", "amph_party_finish", "amph_party_finish_b64",
             "amph_party_free", "amph_party_begin_dev", "amph_party_text_dev", "amph_party_partner_dev",
             "amph_party_finish_b64_dev", "amph_party_reset_partner"]
@@ -450,6 +455,35 @@ class Context:
                                            _ptr(out), flags, stream))
         return out
 
+    def convert_share_json(self, text, tuples32, mac_key: int, use_zero_input_as_data: bool):
+        """amph_convert_share_json: the MaskedInput "data" array text in the
+        compact layout ('[' + 37-byte records + ']', one record per tuple) ->
+        SecretShare.data (W, 32).  Host text (str / bytes / uint8 array): an
+        offending byte or a wrong length raises AmphoraNativeError
+        (AMPH_E_PARAM / AMPH_E_LEN).  Device uint8 tensor (1-D, any byte
+        alignment, e.g. a view into a request body) -> (share, bad) device
+        tensors, bad = AMPH_NO_FAILURE when the text held: check it before
+        storing the share."""
+        if isinstance(text, str):
+            text = text.encode("utf-8")
+        if _is_dev(text):
+            a = text.reshape(-1)
+            if not a.is_contiguous():
+                raise ValueError("the text must be a contiguous uint8 tensor")
+        elif isinstance(text, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(bytes(text), np.uint8)
+        else:
+            a = np.ascontiguousarray(text, np.uint8).reshape(-1)
+        t = words_view(tuples32, 32)
+        flags, stream = self._mode(a, t)
+        W = t.shape[0]
+        out = self._empty(t, (W, 32))
+        bad, badp = self._ff(t)
+        n = a.numel() if _is_dev(a) else a.size
+        self._check(lib.amph_convert_share_json(self._h, _ptr(a), n, W, _ptr(t), le16(mac_key % self.prime),
+                                                int(use_zero_input_as_data), _ptr(out), badp, flags, stream))
+        return (out, bad) if _is_dev(a) else out
+
     def odo_pre(self, share_data, share_stride: int, masks32, triples96):
         sd = words_view(share_data, share_stride)
         mk, tr = words_view(masks32, 32), words_view(triples96, 96)
@@ -574,6 +608,26 @@ class Context:
             raise ValueError(lib.amph_last_error().decode())
         self._check(st, allow_verify=True)
         return o16, o24, self._ff_value(ff), self._ff_value(bad)
+
+    def mask_input_json(self, texts, words: int, secrets16):
+        """amph_mask_input_json: (text, first_fail, bad_char) -- mask_input_b64
+        with the records written as the MaskedInput "data" array text
+        ([{"value":"..."},...], 37 S + 1 characters).  Host: text is bytes;
+        device: a uint8 tensor that stays on the device."""
+        arr, keep = self._text_structs(texts)
+        sv = words_view(secrets16)
+        flags, stream = self._mode(sv, *keep)
+        S = sv.shape[0]
+        cap = lib.amph_masked_input_data_chars(S)
+        out = self._empty(sv, (cap,))
+        ff, ffp = self._ff(sv)
+        bad, badp = self._ff(sv)
+        st = lib.amph_mask_input_json(self._h, arr, len(texts), words, _ptr(sv), S, _ptr(out), cap,
+                                      ffp, badp, flags, stream)
+        if st == AMPH_E_PARAM and not _is_dev(sv) and self._ff_value(bad) >= 0:
+            raise ValueError(lib.amph_last_error().decode())
+        self._check(st, allow_verify=True)
+        return (out if _is_dev(sv) else out.tobytes()), self._ff_value(ff), self._ff_value(bad)
 
     # -- wire codec (base64 as Jackson writes byte[]) ---------------------------
     def base64_encode(self, data) -> bytes:

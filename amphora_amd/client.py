@@ -264,6 +264,27 @@ def create_masked_input_json(util: SecretShareUtil, secret: Secret, odo_bodies: 
     return wire.records_to_masked_input_json(secret.secret_id, rec, secret.tags)
 
 
+def create_masked_input_body(util: SecretShareUtil, secret: Secret, odo_bodies: Sequence[str]) -> str:
+    """create_masked_input_json with the "data" array text written by the
+    kernel itself (amph_mask_input_json): the records leave the GPU already
+    framed as [{"value":"..."},...], so no host pass frames them.  Same body,
+    same exceptions."""
+    import json
+    from . import wire
+    texts, W = _texts_and_words(odo_bodies)
+    try:
+        data, ff, _ = _wire_call(util.context.mask_input_json, texts, W, pack(secret.data, util.prime))
+    except AmphoraClientException as e:
+        if secret.size() > W and isinstance(e.__cause__, _lib.AmphoraNativeError) \
+                and e.__cause__.status == _lib.AMPH_E_LEN:
+            raise IndexError("Index %d out of bounds for length %d" % (W, W)) from e.__cause__
+        raise
+    if ff >= 0:
+        _raise_for_texts(util, texts, ff)
+    tj = json.dumps([wire._tag_obj(t) for t in secret.tags], separators=(",", ":"))
+    return '{"secretId":"%s","data":%s,"tags":%s}' % (secret.secret_id, data.decode("ascii"), tj)
+
+
 def get_secret_data(util: SecretShareUtil, odos: Sequence[OutputDeliveryObject]) -> List[int]:
     """getSecret :206-217 arithmetic (alias of verify_output_delivery_objects)."""
     return verify_output_delivery_objects(util, odos)

@@ -2071,9 +2071,15 @@ int amph_recombine_verify_b64(amph_ctx* c, const amph_odo_b64* odos, int n, size
   return AMPH_OK;
 }
 
-int amph_mask_input_b64(amph_ctx* c, const amph_odo_b64* odos, int n, size_t words,
-                        const uint8_t* secrets, size_t n_secrets, uint8_t* out16, char* out24,
-                        int64_t* first_fail, int64_t* bad_char, uint32_t flags, void* stream) {
+size_t amph_masked_input_data_chars(size_t words) { return words ? 37 * words + 1 : 2; }
+
+// amph_mask_input_b64 / amph_mask_input_json: out_text (the framed "data"
+// array, amph_masked_input_data_chars(n_secrets) characters) excludes the
+// other two outputs.
+static int mask_input_wire(amph_ctx* c, const amph_odo_b64* odos, int n, size_t words,
+                           const uint8_t* secrets, size_t n_secrets, uint8_t* out16, char* out24,
+                           char* out_text, size_t out_cap, int64_t* first_fail, int64_t* bad_char,
+                           uint32_t flags, void* stream) {
   if (check_ctx(c)) return AMPH_E_PARAM;
   AMPH_NO_HOST_IO(flags);
   size_t nchars;
@@ -2097,6 +2103,11 @@ int amph_mask_input_b64(amph_ctx* c, const amph_odo_b64* odos, int n, size_t wor
     return fail(AMPH_E_LEN, "more secret words than verified input masks");
   }
   if (n_secrets && !secrets) return fail(AMPH_E_PARAM, "null secrets");
+  const size_t text_chars = amph_masked_input_data_chars(n_secrets);
+  if (out_text && out_cap < text_chars)
+    return fail(AMPH_E_LEN, "output capacity " + std::to_string(out_cap) + " below the " +
+                                std::to_string(text_chars) + " characters of " + std::to_string(n_secrets) +
+                                " records");
   HIP_TRY(use_device(c->device));
   if (flags & AMPH_F_DEVICE) {
     amph::TextSet tx{};
@@ -2105,10 +2116,20 @@ int amph_mask_input_b64(amph_ctx* c, const amph_odo_b64* odos, int n, size_t wor
         tx.t[k][j] = b64_field(odos[j], k);
         if (int st = check_dev_words({tx.t[k][j]})) return st;
       }
-    if (int st = check_dev_words({secrets, out16, out24})) return st;
+    if (int st = check_dev_words({secrets, out16, out24, out_text})) return st;
     hipStream_t s = (hipStream_t)stream;
     if (int st = reset_ff_dev(first_fail, flags, s)) return st;
     if (int st = reset_ff_dev(bad_char, flags, s)) return st;
+    if (out_text && n_secrets) {
+      hipError_t e = amph::launch_mask_json(tx, n, words, nchars, pad, (const uint4*)secrets, n_secrets, out_text,
+                                            (unsigned long long*)first_fail, (unsigned long long*)bad_char,
+                                            c->f, cfg(c, s, words));
+      return e == hipSuccess ? AMPH_OK : hip_fail(e, "k_mask_json");
+    }
+    if (out_text) {  // no secrets: "[]", and the masks are still verified
+      HIP_TRY(hipMemsetAsync(out_text, '[', 1, s));
+      HIP_TRY(hipMemsetAsync(out_text + 1, ']', 1, s));
+    }
     hipError_t e = amph::launch_mask_b64(tx, n, words, nchars, pad, (const uint4*)secrets, n_secrets,
                                          (uint4*)out16, out24, (unsigned long long*)first_fail,
                                          (unsigned long long*)bad_char, c->f, cfg(c, s, words));
@@ -2116,24 +2137,34 @@ int amph_mask_input_b64(amph_ctx* c, const amph_odo_b64* odos, int n, size_t wor
   }
   if (first_fail) *first_fail = -1;
   if (bad_char) *bad_char = -1;
+  if (out_text && n_secrets == 0) {
+    out_text[0] = '[';
+    out_text[1] = ']';
+    out_text = nullptr;
+  }
   if (words == 0) return AMPH_OK;
   std::lock_guard<std::mutex> g(c->mu);
   hipStream_t s;
   if (int st = host_stream0(c, &s)) return st;
   WireHost h;
-  const size_t extra = 3 * align256(16 * n_secrets) + align256(24 * n_secrets) + 1024;
+  const size_t extra = 3 * align256(16 * n_secrets) + align256(24 * n_secrets) +
+                       (out_text ? align256(text_chars) : 0) + 1024;
   if (int st = h.stage(c, odos, n, nchars, extra, s)) return st;
   uint8_t* dsec = h.take(16 * n_secrets);
   uint8_t* d16 = h.take(16 * n_secrets);
   uint8_t* d24 = h.take(24 * n_secrets);
+  uint8_t* dtext = out_text ? h.take(text_chars) : nullptr;
   if (n_secrets) HIP_TRY(h.put(dsec, secrets, 16 * n_secrets));
-  hipError_t e = amph::launch_mask_b64(h.tx, n, words, nchars, pad, (const uint4*)dsec, n_secrets,
-                                       out16 ? (uint4*)d16 : nullptr, out24 ? (char*)d24 : nullptr,
-                                       h.fl, h.fl + 1, c->f, cfg(c, s, words));
-  if (e != hipSuccess) return h.launch_failed(c, s, e, "k_mask_b64");
+  hipError_t e = out_text ? amph::launch_mask_json(h.tx, n, words, nchars, pad, (const uint4*)dsec, n_secrets,
+                                                   (char*)dtext, h.fl, h.fl + 1, c->f, cfg(c, s, words))
+                          : amph::launch_mask_b64(h.tx, n, words, nchars, pad, (const uint4*)dsec, n_secrets,
+                                                  out16 ? (uint4*)d16 : nullptr, out24 ? (char*)d24 : nullptr,
+                                                  h.fl, h.fl + 1, c->f, cfg(c, s, words));
+  if (e != hipSuccess) return h.launch_failed(c, s, e, out_text ? "k_mask_json" : "k_mask_b64");
   int64_t v[2];
   if (int st = h.finish(c, s, v, {{out16, d16, out16 ? 16 * n_secrets : 0},
-                                  {out24, d24, out24 ? 24 * n_secrets : 0}}))
+                                  {out24, d24, out24 ? 24 * n_secrets : 0},
+                                  {out_text, dtext, out_text ? text_chars : 0}}))
     return st;
   if (v[1] != (int64_t)AMPH_NO_FAILURE) {
     if (bad_char) *bad_char = v[1];
@@ -2143,6 +2174,70 @@ int amph_mask_input_b64(amph_ctx* c, const amph_odo_b64* odos, int n, size_t wor
     if (first_fail) *first_fail = v[0];
     return AMPH_E_VERIFY;
   }
+  return AMPH_OK;
+}
+
+int amph_mask_input_b64(amph_ctx* c, const amph_odo_b64* odos, int n, size_t words,
+                        const uint8_t* secrets, size_t n_secrets, uint8_t* out16, char* out24,
+                        int64_t* first_fail, int64_t* bad_char, uint32_t flags, void* stream) {
+  return mask_input_wire(c, odos, n, words, secrets, n_secrets, out16, out24, nullptr, 0, first_fail, bad_char,
+                         flags, stream);
+}
+
+int amph_mask_input_json(amph_ctx* c, const amph_odo_b64* odos, int n, size_t words,
+                         const uint8_t* secrets, size_t n_secrets, char* out_text, size_t out_cap,
+                         int64_t* first_fail, int64_t* bad_char, uint32_t flags, void* stream) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  if (!out_text && n_secrets <= words) return fail(AMPH_E_PARAM, "null output text");
+  return mask_input_wire(c, odos, n, words, secrets, n_secrets, nullptr, nullptr, out_text, out_cap, first_fail,
+                         bad_char, flags, stream);
+}
+
+// ---- K_CONV from the MaskedInput "data" array text -------------------------------
+int amph_convert_share_json(amph_ctx* c, const char* text, size_t len, size_t words,
+                            const uint8_t* tuples, const uint8_t mac_key_le[16], int use_zero,
+                            uint8_t* out, int64_t* bad_index, uint32_t flags, void* stream) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  AMPH_NO_HOST_IO(flags);
+  if (!mac_key_le) return fail(AMPH_E_PARAM, "null mac key");
+  if (len != amph_masked_input_data_chars(words))
+    return fail(AMPH_E_LEN, "data array text of " + std::to_string(len) + " characters, expected " +
+                                std::to_string(amph_masked_input_data_chars(words)) + " for " +
+                                std::to_string(words) + " compact records");
+  if (!text || (words && (!tuples || !out))) return fail(AMPH_E_PARAM, "null buffer");
+  const W4 alpha = amph::mont_mul(w4_of(ld128(mac_key_le)), amph::r2_word(c->f), c->f);
+  HIP_TRY(use_device(c->device));
+  if (flags & AMPH_F_DEVICE) {  // the text at any byte alignment
+    if (int st = check_dev_words({tuples, out})) return st;
+    hipStream_t s = (hipStream_t)stream;
+    if (int st = reset_ff_dev(bad_index, flags, s)) return st;
+    hipError_t e = amph::launch_convert_share_json(text, (const uint4*)tuples, words, alpha, use_zero, (uint4*)out,
+                                                   (unsigned long long*)bad_index, c->f, cfg(c, s, words));
+    return e == hipSuccess ? AMPH_OK : hip_fail(e, "k_conv_json");
+  }
+  // host mode: one shot on the context's first stream, as the exchange codec
+  if (bad_index) *bad_index = -1;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipStream_t s;
+  if (int st = host_stream0(c, &s)) return st;
+  XStage x;
+  const size_t sizes[4] = {len, 32 * words, 32 * words, 8};
+  if (int st = x.stage(c, sizes, 4)) return st;
+  void *dtext = x.take(sizes[0]), *dtup = x.take(sizes[1]), *dout = x.take(sizes[2]), *dbad = x.take(sizes[3]);
+  HIP_TRY(hipMemcpy(dtext, text, len, hipMemcpyHostToDevice));
+  if (words) HIP_TRY(hipMemcpy(dtup, tuples, 32 * words, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(dbad, 0x7F, 8, s));
+  hipError_t e = amph::launch_convert_share_json((const char*)dtext, (const uint4*)dtup, words, alpha, use_zero,
+                                                 (uint4*)dout, (unsigned long long*)dbad, c->f, cfg(c, s, words));
+  if (e != hipSuccess) return hip_fail(e, "k_conv_json");
+  int64_t bad = 0;
+  HIP_TRY(read_back(s, {{&bad, dbad, 8}}));
+  if (bad != (int64_t)AMPH_NO_FAILURE) {
+    if (bad_index) *bad_index = bad;
+    const std::string where = bad == 0 ? "the leading '['" : "record " + std::to_string((bad - 1) / 37);
+    return fail(AMPH_E_PARAM, "Malformed MaskedInput data text at offset " + std::to_string(bad) + " (" + where + ")");
+  }
+  HIP_TRY(read_back(s, {{out, dout, 32 * words}}));
   return AMPH_OK;
 }
 

@@ -199,6 +199,119 @@ __global__ __launch_bounds__(kPairBlock) void k_conv(const uint4* masked, const 
   }
 }
 
+// K_CONV from the wire: the "data" array of a MaskedInput body as Jackson
+// writes it, '[' + one 37-byte record {"value":"<24 base64 chars>"} per word,
+// ',' between records, ']' (MaskedInput.java:25-62, MaskedInputData.java:44-52),
+// decoded on chip and converted as k_conv does: the masked words never reach
+// HBM (37 + 32 + 32 B per word where k_b64_unwords + k_conv move 120).
+//
+// A workgroup owns kPairBlock records and the byte in front of them: 37 x 128
+// bytes = 296 16-byte granules, so every workgroup's window starts at the
+// same offset `shift` = text & 15 into a granule.  The aligned granules that
+// hold the window (at most kJsonGran; each holds at least one byte of the
+// text) move as coalesced 16-byte loads into LDS; lane t then reads the 11
+// dwords around its record at shift + 1 + 37 t, realigns them with
+// v_alignbyte and checks the 13 frame bytes and the 24 characters (accepted
+// exactly as k_b64_unwords accepts a record).  bad: the smallest byte offset
+// in the text of an offending byte.
+constexpr int kJsonRec = 37;  // bytes per record, its trailing ',' / ']' included
+constexpr int kJsonGran = (15 + kJsonRec * kPairBlock + 1 + 15) / 16;  // 297
+
+// (rare) the offset in its record of the first byte the record's frame or
+// base64 rule refuses, or 0xFFFFFFFF; w = the record's 37 bytes as dwords
+__device__ __forceinline__ uint32_t json_record_bad(const uint32_t (&w)[10], bool last) {
+  const char frame[] = "{\"value\":\"";
+  uint32_t fb = 0xFFFFFFFFu;
+#pragma unroll
+  for (int k = kJsonRec - 1; k >= 0; --k) {
+    const uint32_t ch = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+    bool ok;
+    if (k < 10) ok = ch == (uint32_t)frame[k];
+    else if (k < 32) ok = (kB64Val.v[ch] & 0x80u) == 0;
+    else if (k < 34) ok = ch == '=';
+    else if (k == 34) ok = ch == '"';
+    else if (k == 35) ok = ch == '}';
+    else ok = ch == (last ? (uint32_t)']' : (uint32_t)',');
+    if (!ok) fb = (uint32_t)k;
+  }
+  return fb;
+}
+
+template <bool BIG>
+__global__ __launch_bounds__(kPairBlock) void k_conv_json(const char* text, const uint4* tuples,
+                                                         size_t words, W4 alpha, int use_zero,
+                                                         uint4* out, unsigned long long* bad, Fp f) {
+  if (words == 0) {  // "[]"
+    if (threadIdx.x < 2 && text[threadIdx.x] != (threadIdx.x ? ']' : '['))
+      atomicMin(bad, (unsigned long long)threadIdx.x);
+    return;
+  }
+  __shared__ uint4 buf[3 * kPairBlock];
+  __shared__ uint4 txt[kJsonGran + 1];  // (+1: the last lane's 11th dword)
+  const size_t i0 = (size_t)blockIdx.x * kPairBlock, i = i0 + threadIdx.x;
+  const size_t nblk = min((size_t)kPairBlock, words - i0);
+  // the window [37 i0, 37 (i0 + nblk)] of the text, from its first granule on
+  const uintptr_t win = (uintptr_t)text + (size_t)kJsonRec * i0;
+  const uint32_t shift = (uint32_t)(win & 15);
+  const uint4* src = reinterpret_cast<const uint4*>(win - shift);
+  const uint32_t ngran = (shift + kJsonRec * (uint32_t)nblk + 1 + 15) >> 4;
+  uint4 tv[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t q = r * kPairBlock + threadIdx.x;
+    tv[r] = make_uint4(0, 0, 0, 0);
+    if (q < ngran) tv[r] = ld(src + q);
+  }
+  stage_tuples<2, kPairBlock>(buf, tuples + 2 * i0, nblk);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t q = r * kPairBlock + threadIdx.x;
+    if (q < (uint32_t)kJsonGran + 1) txt[q] = tv[r];
+  }
+  __syncthreads();
+  if (i < words) {
+    const uint32_t* tw = reinterpret_cast<const uint32_t*>(txt);
+    const uint32_t o = shift + 1 + kJsonRec * threadIdx.x, d0 = o >> 2, sub = o & 3;
+    uint32_t d[11], w[10], x[6];
+#pragma unroll
+    for (int j = 0; j < 11; ++j) d[j] = tw[d0 + j];
+#pragma unroll
+    for (int j = 0; j < 10; ++j) w[j] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], sub);
+    // the 24 characters start at byte 10 of the record
+#pragma unroll
+    for (int q = 0; q < 6; ++q) x[q] = __builtin_amdgcn_alignbyte(w[q + 3], w[q + 2], 2);
+    const DecTabs tabs = dec_tabs_vgpr();
+    uint32_t ok = 0x80808080u, b[3];
+    dec_unit16_ok(make_uint4(x[0], x[1], x[2], x[3]), b, ok, tabs);
+    // as k_b64_unwords: the final "==" decode as 'A', the unused low bits of
+    // character 21 are ignored
+    const uint32_t v4 = dec4_values6(x[4], ok, tabs), v5 = dec4_values6((x[5] & 0xFFFFu) | 0x41410000u, ok, tabs);
+    const uint32_t g4 = (__builtin_amdgcn_udot4(v4, 0x00000140u, 0u, false) << 12) |
+                        __builtin_amdgcn_udot4(v4, 0x01400000u, 0u, false);
+    const uint32_t g5 = __builtin_amdgcn_udot4(v5, 0x00000140u, 0u, false) << 12;
+    const uint4 mr = make_uint4(b[0], b[1], b[2], __builtin_amdgcn_perm(g5, g4, 0x06000102u));
+    const bool last = i + 1 == words;
+    const bool framed = (int)(w[0] == 0x6176227Bu) & (int)(w[1] == 0x2265756Cu) & (int)((w[2] & 0xFFFFu) == 0x223Au) &
+                        (int)((w[8] >> 16) == 0x7D22u) & (int)((w[9] & 0xFFu) == (last ? 0x5Du : 0x2Cu));
+    if (!framed || ok != 0x80808080u || (x[5] >> 16) != 0x3D3Du) {
+      const uint32_t fb = json_record_bad(w, last);
+      if (fb != 0xFFFFFFFFu) atomicMin(bad, (unsigned long long)(1 + kJsonRec * i + fb));
+    }
+    if (i == 0 && ((tw[shift >> 2] >> (8 * (shift & 3))) & 0xFFu) != '[') atomicMin(bad, 0ULL);
+    const W4 m = canon<BIG>(w4(mr), f);
+    const W4 val = canon<BIG>(w4(buf[3 * threadIdx.x]), f);
+    const W4 mac = canon<BIG>(w4(buf[3 * threadIdx.x + 1]), f);
+    buf[3 * threadIdx.x] = u4(use_zero ? val : mod_add(val, m, f));
+    buf[3 * threadIdx.x + 1] = u4(mod_add(mac, mont_mul(m, alpha, f), f));
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const size_t q = (size_t)r * kPairBlock + threadIdx.x;
+    if (q < 2 * nblk) st_party(out + 2 * i0 + q, buf[(q >> 1) * 3 + (q & 1)]);
+  }
+}
+
 // K_ODO_PRE, one Beaver pair per lane (k = 2i: (y_i, r_i), k = 2i+1: (v_i, r_i);
 // r_i = value of mask tuple 2i, v_i = value of mask tuple 2i+1), the
 // workgroup's triples (96 B) and mask tuples (32 B) staged through LDS.
@@ -674,6 +787,15 @@ hipError_t launch_convert_share(const uint4* masked, const uint4* tuples, size_t
   const dim3 g((unsigned)((words + kPairBlock - 1) / kPairBlock));
   if (f.big) AMPH_LAUNCH((k_conv<true>), g, dim3(kPairBlock), c, masked, tuples, words, alpha, use_zero, out, f);
   else AMPH_LAUNCH((k_conv<false>), g, dim3(kPairBlock), c, masked, tuples, words, alpha, use_zero, out, f);
+  return hipGetLastError();
+}
+
+hipError_t launch_convert_share_json(const char* text, const uint4* tuples, size_t words, W4 alpha,
+                                     int use_zero, uint4* out, unsigned long long* bad, const Fp& f,
+                                     const LaunchCfg& c) {
+  const dim3 g((unsigned)(words ? (words + kPairBlock - 1) / kPairBlock : 1));  // (no words: "[]" is checked)
+  if (f.big) AMPH_LAUNCH((k_conv_json<true>), g, dim3(kPairBlock), c, text, tuples, words, alpha, use_zero, out, bad, f);
+  else AMPH_LAUNCH((k_conv_json<false>), g, dim3(kPairBlock), c, text, tuples, words, alpha, use_zero, out, bad, f);
   return hipGetLastError();
 }
 

@@ -96,6 +96,13 @@ hipError_t launch_convert_share(const uint4* masked, const uint4* tuples, size_t
                                 W4 alpha_mont, int use_zero_input, uint4* out, const Fp& f,
                                 const LaunchCfg& c);
 
+// K_CONV from the MaskedInput "data" array text (37 words + 1 characters, any
+// byte alignment; "[]" for no words): bad = min byte offset of an offending
+// frame byte or base64 character; the output is unspecified when it is set.
+hipError_t launch_convert_share_json(const char* text, const uint4* tuples, size_t words, W4 alpha_mont,
+                                     int use_zero_input, uint4* out, unsigned long long* bad,
+                                     const Fp& f, const LaunchCfg& c);
+
 // K_ODO_PRE: raw y/r/v copies (each optional) + signed Beaver diffs; with
 // lens, also the exchange text length of every kXLenPairs FactorPairs
 // (launch_exchange_encode_lens' input).
@@ -184,6 +191,13 @@ hipError_t launch_mask_b64(const TextSet& tx, int n, size_t words, size_t nchars
                            const uint4* secrets, size_t n_secrets, uint4* out16, char* out24,
                            unsigned long long* first_fail, unsigned long long* bad, const Fp& f,
                            const LaunchCfg& c);
+// launch_mask_b64 with the records framed as the MaskedInput "data" array
+// text: out_text (16-byte aligned) gets 37 n_secrets + 1 characters; n_secrets
+// in [1, words] (the caller writes "[]" for none)
+hipError_t launch_mask_json(const TextSet& tx, int n, size_t words, size_t nchars, uint32_t pad,
+                            const uint4* secrets, size_t n_secrets, char* out_text,
+                            unsigned long long* first_fail, unsigned long long* bad, const Fp& f,
+                            const LaunchCfg& c);
 
 // Small host calls: copy n verdict words from device memory to page-locked
 // host memory and reset them to kNoFail (one 64-lane workgroup).

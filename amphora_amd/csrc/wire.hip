@@ -172,10 +172,24 @@ __device__ __forceinline__ void wire_load(const TextSet& tx, uint4 (&raw)[5][NP 
   }
 }
 
+// The framed form of the records: the "data" array text of the MaskedInput
+// body as Jackson writes it (MaskedInput.java:25-62, MaskedInputData.java:
+// 44-52), '[' + {"value":"<24 chars>"} per secret, ',' between, ']'.
+constexpr int kJsonRec = 37;  // bytes per record, its ',' / ']' included
+
 // K_MASK from the wire, after a tile's fields are summed: verify, mask the
 // secret, and write the masked word and / or its 24-character record (each
 // lane its own, as three nontemporal 8-byte stores).
-template <int NP, int BS>
+//
+// JSON: out24 is the framed text instead.  The workgroup owns the 37 WW
+// bytes (a whole number of 16-byte runs) from the ',' / '[' in front of its
+// first record on; the workgroup of the last secret also owns the ']'.  The
+// image is built in LDS (lds: the decode buffers, free after a barrier) --
+// each lane writes the aligned dwords that START inside its record, whose
+// bytes past the record are the next record's constant {"v -- and leaves as
+// coalesced nontemporal 16-byte runs; the text's final partial run byte by
+// byte, so nothing past the ']' is written.
+template <int NP, int BS, bool JSON = false>
 __device__ __forceinline__ void mask_tile_out(size_t tile, size_t words, const uint4 s, size_t n_secrets,
                                               W4 (&acc)[5], uint4* out16, char* out24,
                                               unsigned long long* ff, uint32_t (*lds)[3 * BS], const Fp& f) {
@@ -190,9 +204,39 @@ __device__ __forceinline__ void mask_tile_out(size_t tile, size_t words, const u
     report_fail(in && !ok, word, ff);
     if (has_secret) {
       const uint4 m = u4(mod_sub(mont_mul_v(w4(s), r2_word(f), f), acc[0], f));
-      if (out16) st_out(out16 + word, w4(m));
+      if (!JSON && out16) st_out(out16 + word, w4(m));
       enc_word24(m, g);
     }
+  }
+  if constexpr (JSON) {
+    static_assert((kJsonRec * WW) % 16 == 0, "a workgroup's records are whole 16-byte runs");
+    const size_t r0 = tile * WW;
+    if (r0 >= n_secrets) return;  // (the whole workgroup)
+    const uint32_t nrec = (uint32_t)min((size_t)WW, n_secrets - r0);
+    const uint32_t total = kJsonRec * nrec + (r0 + nrec == n_secrets ? 1u : 0u);
+    uint32_t* img = &lds[0][0];
+    __syncthreads();  // every lane is past its last read of the decode buffers
+    if (has_secret) {
+      constexpr uint32_t kOpen = 0x76227B00u;  // {"v in bytes 1-3
+      const uint32_t r[10] = {0x6176227Bu, 0x2265756Cu, 0x223Au | (g[0] << 16),
+                              (g[0] >> 16) | (g[1] << 16), (g[1] >> 16) | (g[2] << 16),
+                              (g[2] >> 16) | (g[3] << 16), (g[3] >> 16) | (g[4] << 16),
+                              (g[4] >> 16) | (g[5] << 16), (g[5] >> 16) | 0x7D220000u,
+                              (word + 1 == n_secrets ? (uint32_t)']' : (uint32_t)',') | kOpen};
+      const uint32_t o = 1 + kJsonRec * threadIdx.x, e = (4 - (o & 3)) & 3, base = (o + 3) >> 2;
+#pragma unroll
+      for (int j = 0; j < 9; ++j) img[base + j] = __builtin_amdgcn_alignbyte(r[j + 1], r[j], e);
+      if (e == 0) img[base + 9] = r[9];
+      if (threadIdx.x == 0) img[0] = (tile == 0 ? (uint32_t)'[' : (uint32_t)',') | kOpen;
+    }
+    __syncthreads();
+    char* dst = out24 + (size_t)kJsonRec * r0;
+    typedef unsigned int ju32x4 __attribute__((ext_vector_type(4)));
+    for (uint32_t q = threadIdx.x; q < total / 16; q += BS)
+      __builtin_nontemporal_store(reinterpret_cast<const ju32x4*>(img)[q], reinterpret_cast<ju32x4*>(dst) + q);
+    const uint32_t done = total & ~15u;
+    if (threadIdx.x < total - done) dst[done + threadIdx.x] = reinterpret_cast<const char*>(img)[done + threadIdx.x];
+    return;
   }
   if (!out24 || !has_secret) return;
   // records: each lane streams its own 24 bytes as three nontemporal 8-byte
@@ -257,8 +301,8 @@ __global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_rv_b64(TextSet tx, int n, 
 // K_MASK from the wire: the N parties' base64 Input Mask ODO fields + the
 // secrets -> verify the masks, masked[i] = toGfp((s_i - m_i) mod p) for
 // i < n_secrets, written as raw words (out16) and/or as the 24-character
-// base64 records of MaskedInputData (out24, staged through LDS and stored as
-// coalesced 16-byte runs).  createSecret, DefaultAmphoraClient.java:150-170.
+// base64 records of MaskedInputData (out24, each lane its own record as three
+// nontemporal 8-byte stores).  createSecret, DefaultAmphoraClient.java:150-170.
 template <int NP, bool BIG, int BS>
 __global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_b64(TextSet tx, int n, size_t words, size_t nchars,
                                              uint32_t pad, const uint4* secrets, size_t n_secrets,
@@ -288,6 +332,38 @@ __global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_b64(TextSet tx, int n
   mask_tile_out<NP, BS>(blockIdx.x, words, s, n_secrets, acc, out16, out24, ff, lds, f);
 }
 
+// k_mask_b64 with the masked words written as the framed "data" array text
+// of the MaskedInput body (mask_tile_out's JSON form): out_text, 16-byte
+// aligned, gets 37 n_secrets + 1 characters (n_secrets >= 1).
+template <int NP, bool BIG, int BS>
+__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_json(TextSet tx, int n, size_t words, size_t nchars,
+                                              uint32_t pad, const uint4* secrets, size_t n_secrets,
+                                              char* out_text, unsigned long long* ff,
+                                              unsigned long long* bad, Fp f) {
+  constexpr int WW = Wire<BS>::words;
+  // (at least 3 buffers: the text image of WW records needs 37 WW + 4 bytes)
+  __shared__ __attribute__((aligned(16))) uint32_t lds[WireGroups<NP>::bufs < 3 ? 3 : WireGroups<NP>::bufs][3 * BS];
+  static_assert(3 * 3 * BS * 4 >= kJsonRec * WW + 4, "the text image fits the decode buffers");
+  __shared__ uint32_t lutw[kLutBytes / 4];
+  uint8_t* lutp = reinterpret_cast<uint8_t*>(lutw);
+  b64_lut_fill(lutp);
+  __syncthreads();
+  W4 acc[5];
+  uint4 raw[5][NP > 0 ? NP : 1];
+  const size_t word = (size_t)blockIdx.x * WW + threadIdx.x;
+  const bool has_secret = threadIdx.x < WW && word < n_secrets;
+  const bool fast = ((size_t)blockIdx.x + 1) * Wire<BS>::chars + 4 <= nchars;
+  if (fast) {
+    wire_load<NP, BS>(tx, raw, blockIdx.x);
+    wire_fields<NP, BIG, true, BS>(tx, n, nchars, pad, words, raw, lds, acc, bad, f, blockIdx.x, lutp);
+  } else {
+    wire_fields<NP, BIG, false, BS>(tx, n, nchars, pad, words, raw, lds, acc, bad, f, blockIdx.x, lutp);
+  }
+  uint4 s = make_uint4(0, 0, 0, 0);  // (after the decode, as k_mask_b64)
+  if (has_secret) s = ld(secrets + word);
+  mask_tile_out<NP, BS, true>(blockIdx.x, words, s, n_secrets, acc, nullptr, out_text, ff, lds, f);
+}
+
 
 }  // namespace
 
@@ -312,6 +388,19 @@ hipError_t launch_mask_b64(const TextSet& tx, int n, size_t words, size_t nchars
   constexpr int BS = kWireBlock;
   const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
 #define L(NP, BIG) AMPH_LAUNCH((k_mask_b64<NP, BIG, BS>), g, dim3(BS), c, tx, n, words, nchars, pad, secrets, n_secrets, out16, out24, ff, bad, f)
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+#undef L
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_json(const TextSet& tx, int n, size_t words, size_t nchars, uint32_t pad,
+                            const uint4* secrets, size_t n_secrets, char* out_text,
+                            unsigned long long* ff, unsigned long long* bad, const Fp& f,
+                            const LaunchCfg& c) {
+  if (words == 0) return hipSuccess;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
+#define L(NP, BIG) AMPH_LAUNCH((k_mask_json<NP, BIG, BS>), g, dim3(BS), c, tx, n, words, nchars, pad, secrets, n_secrets, out_text, ff, bad, f)
   if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
 #undef L
   return hipGetLastError();

@@ -31,10 +31,11 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Dict, List, Sequence
 
 from . import _lib
-from .client import (SecretShareUtil, create_masked_input, create_masked_input_json,
-                     verify_output_delivery_objects, verify_vss_json)
-from .entities import (AmphoraClientException, AmphoraServiceException, FactorPair, MaskedInput,
-                       MultiplicationExchangeObject, OutputDeliveryObject, Secret, SecretShare)
+from .client import (SecretShareUtil, create_masked_input, create_masked_input_body,
+                     create_masked_input_json, verify_output_delivery_objects, verify_vss_json)
+from .entities import (AmphoraClientException, AmphoraServiceException, FactorPair,
+                       IllegalArgumentException, MaskedInput, MultiplicationExchangeObject,
+                       OutputDeliveryObject, Secret, SecretShare)
 from .service import INPUT_MASK_GFP, OutputDeliveryService
 from .service import SecretShareUtil as ServiceSecretShareUtil
 
@@ -107,6 +108,30 @@ class AmphoraParty:
         del self.input_mask_store[masked_input.secret_id]
         return masked_input.secret_id
 
+    # POST /masked-inputs, from the request body's text
+    def upload_masked_input_body(self, body) -> uuid.UUID:
+        """upload_masked_input on the MaskedInput JSON body itself: the "data"
+        array goes to the fused conversion as text
+        (service.SecretShareUtil.convert_masked_input_json); a body in another
+        layout is parsed first, as upload_masked_input's caller does."""
+        import json
+        from . import wire
+        raw = body.encode("utf-8") if isinstance(body, str) else bytes(body)
+        span = wire.masked_input_data_span(raw)
+        if span is None:
+            return self.upload_masked_input(wire.masked_input_from_json(self.ctx, raw.decode("utf-8")))
+        sid = json.loads(span[2]).get("secretId")
+        if sid is None:
+            raise IllegalArgumentException("secretId is marked non-null but is null")
+        sid = uuid.UUID(sid)
+        masks = self.input_mask_store.get(sid)
+        if masks is None:
+            raise AmphoraServiceException(NO_INPUT_MASKS_FOUND_FOR_REQUEST_ID_EXCEPTION_MSG % sid)
+        self.secrets[sid] = self.share_util.convert_masked_input_json(
+            raw, str(self.mac_key), masks, self.player_id != 0)
+        del self.input_mask_store[sid]
+        return sid
+
     # GET /secret-shares/{id}?requestId
     def get_secret_share(self, secret_id: uuid.UUID, request_id: uuid.UUID) -> OutputDeliveryObject:
         return self.odo_service.compute_output_delivery_object(self.secrets[secret_id], request_id)
@@ -122,9 +147,13 @@ class LoopbackAmphoraClient:
         would (OutputDeliveryObject / VerifiableSecretShare / MaskedInput,
         base64 coded on the parties' GPUs), and the client consumes and
         produces the text with the fused wire kernels (client.verify_vss_json,
-        client.create_masked_input_json)."""
-        if transport not in ("objects", "json"):
-            raise ValueError("transport must be 'objects' or 'json'")
+        client.create_masked_input_json).
+        transport="wire": as "json", but the upload hop stays text at both
+        ends: the client's kernel writes the framed "data" array
+        (client.create_masked_input_body) and every party converts the body's
+        text (AmphoraParty.upload_masked_input_body)."""
+        if transport not in ("objects", "json", "wire"):
+            raise ValueError("transport must be 'objects', 'json' or 'wire'")
         self.parties = list(parties)
         self.util = SecretShareUtil.of(prime, r, r_inv, device)
         self.transport = transport
@@ -164,6 +193,13 @@ class LoopbackAmphoraClient:
             raise AmphoraClientException(msg)
 
     def create_secret(self, secret: Secret) -> uuid.UUID:
+        if self.transport == "wire":
+            from . import wire
+            bodies = self._unwrap(self._fan_out(lambda p: wire.odo_to_json(
+                p.ctx, p.get_input_masks(secret.secret_id, secret.size()))))
+            text = create_masked_input_body(self.util, secret, bodies)
+            self._check_success(self._fan_out(lambda p: p.upload_masked_input_body(text)))
+            return secret.secret_id
         if self.transport == "json":
             from . import wire
             bodies = self._unwrap(self._fan_out(lambda p: wire.odo_to_json(
@@ -179,7 +215,7 @@ class LoopbackAmphoraClient:
 
     def get_secret(self, secret_id: uuid.UUID) -> Secret:
         request_id = uuid.uuid4()
-        if self.transport == "json":
+        if self.transport in ("json", "wire"):
             from . import wire
             bodies = self._unwrap(self._fan_out(lambda p: wire.vss_to_json(
                 p.ctx, secret_id, p.secrets[secret_id].tags, p.get_secret_share(secret_id, request_id),

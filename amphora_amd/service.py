@@ -65,6 +65,40 @@ class SecretShareUtil:
         out = self._ctx.convert_share(masked, masks, key, use_zero_input_as_data)
         return SecretShare(masked_input.secret_id, out.tobytes(), list(masked_input.tags))
 
+    def convert_masked_input_json(self, body, mac_key: str, input_masks,
+                                  use_zero_input_as_data: bool) -> SecretShare:
+        """POST /masked-inputs on the body text (MaskedInputController.upload ->
+        StorageService.createSecret -> convertToSecretShare :58-107): when the
+        "data" array is in Jackson's compact layout with one record per input
+        mask, one launch (amph_convert_share_json) checks, decodes and converts
+        it and only the small remainder of the body goes through json.loads.
+        Any other body -- another legal layout, a record count other than the
+        mask count, a byte the kernel refuses -- takes
+        wire.masked_input_from_json + convert_to_secret_share, so it gets the
+        reference's verdict and message."""
+        from . import wire
+        masks = _tuples(input_masks, 32)
+        raw = body.encode("utf-8") if isinstance(body, str) else bytes(body)
+        span = wire.masked_input_data_span(raw)
+        if span is not None:
+            lb, rb, rest = span
+            if rb + 1 - lb == (37 * masks.shape[0] + 1 if masks.shape[0] else 2):
+                try:
+                    out = self._ctx.convert_share_json(raw[lb:rb + 1], masks, int(mac_key) % self._ctx.prime,
+                                                       use_zero_input_as_data)
+                except _lib.AmphoraNativeError as e:
+                    if e.status not in (_lib.AMPH_E_LEN, _lib.AMPH_E_PARAM):
+                        raise
+                    out = None
+                if out is not None:
+                    import json
+                    obj = json.loads(rest)
+                    if obj.get("secretId") is None:
+                        raise IllegalArgumentException("secretId is marked non-null but is null")
+                    return SecretShare(uuid.UUID(obj["secretId"]), out.tobytes(), list(obj.get("tags") or []))
+        mi = wire.masked_input_from_json(self._ctx, raw.decode("utf-8"))
+        return self.convert_to_secret_share(mi, mac_key, input_masks, use_zero_input_as_data)
+
 
 def _tuples(x, size):
     if isinstance(x, (list, tuple)):

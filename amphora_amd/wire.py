@@ -9,7 +9,10 @@ base64-coded on the GPU (amph_base64_*).
 * OutputDeliveryObject JSON (GET /input-masks): the five base64 fields.
 * MaskedInput JSON (POST /masked-inputs): MaskedInput.java:25-62 --
   {"secretId", "data": [{"value": base64(16 bytes)}, ...], "tags"}; each word
-  is coded on its own (24 chars), the records are framed with numpy.
+  is coded on its own (24 chars), the records are framed with numpy -- or by
+  the kernels themselves, at both ends, when the "data" array is in Jackson's
+  compact layout (masked_input_data_span, amph_mask_input_json /
+  amph_convert_share_json).
 
 Large payloads: the base64 spans are located by a structural walk of the
 outermost object that skips strings whole (no JSON tree is built for them);
@@ -268,6 +271,55 @@ def _compact_records(text: str):
             and (b[:, 34] == ord('"')).all() and (b[:, 35] == ord("}")).all() and (b[:, 36] == ord(",")).all()):
         return None
     return np.ascontiguousarray(b[:, 10:34]), text[:lb] + "[]" + text[rb + 1:]
+
+
+def _depth_at(text: str, k: int) -> int:
+    """Nesting depth of position k of a JSON text, -1 if k lies inside a string
+    (the structural walk of _top_level_members, stopped at k)."""
+    depth, pos = 0, 0
+    while True:
+        m = _SIGNIFICANT.search(text, pos, k)
+        if m is None:
+            return depth
+        c, i = m.group(), m.start()
+        if c == '"':
+            e = _string_end(text, i)
+            if e >= k:
+                return -1
+            pos = e + 1
+        else:
+            depth += 1 if c in "{[" else -1
+            pos = i + 1
+
+
+def masked_input_data_span(body):
+    """(lb, rb, rest) of a MaskedInput body (bytes, or str taken as UTF-8):
+    body[lb:rb + 1] is the '['..']' array text of the one "data" member of the
+    outermost object as the compact layout writes it, rest the body with that
+    array emptied ("[]"; json.loads takes it).  None when the body is not
+    written that way -- no '"data":[' at the top level, the key more than
+    once, no ']' -- and the general parser has to take it.  The sibling of
+    exchange_span, for amph_convert_share_json.
+
+    The array is cut at the first ']' after its '[': in the compact layout no
+    record holds one, and the fused call accepts the span only if every byte
+    of it is a record's, so a span cut short by a ']' inside a string is
+    refused there, never converted."""
+    raw = body.encode("utf-8") if isinstance(body, str) else bytes(body)
+    text = raw.decode("latin-1")  # one character per byte: offsets are byte offsets
+    k = text.find('"data":[')
+    if k < 0 or text.count('"data"') != 1:
+        return None
+    try:
+        if _depth_at(text, k) != 1:  # a nested member, or the inside of a string
+            return None
+    except ValueError:
+        return None
+    lb = k + len('"data":')
+    rb = text.find("]", lb)
+    if rb < 0:
+        return None
+    return lb, rb, raw[:lb] + b"[]" + raw[rb + 1:]
 
 
 def masked_input_from_json(ctx: _lib.Context, text: str) -> MaskedInput:

@@ -420,6 +420,48 @@ int amph_mask_input_b64(amph_ctx* ctx, const amph_odo_b64* mask_odos, int n_part
                         char* out_records24, int64_t* first_fail, int64_t* bad_char, uint32_t flags,
                         void* stream);
 
+/* ---- the Input Supply upload on the MaskedInput JSON text ------------------
+ * POST /masked-inputs carries a MaskedInput (MaskedInput.java:25-62) whose
+ * "data" member is the list of MaskedInputData (MaskedInputData.java:44-52).
+ * Jackson writes that list as '[' + one 37-byte record {"value":"<24 base64
+ * characters>"} per word, ',' between records, ']': 37 * words + 1
+ * characters ("[]" for no words).  The two calls below take and give exactly
+ * this compact layout (characters 0..21 of a record in the standard
+ * alphabet, 22 and 23 '=', the unused low bits of character 21 ignored, as
+ * amph_base64_decode_words); any other legal JSON layout is for the caller
+ * to parse and hand to amph_convert_share.
+ *
+ * amph_convert_share_json: the party's side, MaskedInputController.upload ->
+ *   StorageService.createSecret -> service SecretShareUtil.convertToSecretShare
+ *   (SecretShareUtil.java:58-107) on the text itself.  One kernel checks every
+ *   frame byte and base64 character, decodes each record on chip and converts
+ *   it as amph_convert_share does; the decoded masked words never reach
+ *   device memory.  len != amph_masked_input_data_chars(words): AMPH_E_LEN,
+ *   nothing launched or written.  bad_index: the byte offset in data_text of
+ *   the first offending byte (frame bytes and base64 characters alike).  Host
+ *   mode: AMPH_E_PARAM with *bad_index set (message names the record and the
+ *   offset), -1 when clean.  Device mode: data_text at ANY byte alignment
+ *   (mask_tuples and out_share 16-byte aligned), asynchronous on `stream`,
+ *   bad_index a device word (AMPH_NO_FAILURE when clean); out_share is
+ *   unspecified when bad_index reports a failure -- check it before storing
+ *   the share.  AMPH_F_HOST_IO is refused (AMPH_E_PARAM).  A multi-device
+ *   context runs the call on its first device.
+ *
+ * amph_mask_input_json: the client's side, amph_mask_input_b64 with the
+ *   records written as that text (amph_masked_input_data_chars(n_secrets)
+ *   characters, no terminator) into out_text; out_cap below that: AMPH_E_LEN.
+ *   Verdict order, first_fail, bad_char and the n_secrets > words path are
+ *   those of amph_mask_input_b64.  Device mode: out_text 16-byte aligned,
+ *   written asynchronously. */
+size_t amph_masked_input_data_chars(size_t words); /* 37 * words + 1, or 2 for 0 */
+int amph_convert_share_json(amph_ctx* ctx, const char* data_text, size_t len, size_t words,
+                            const uint8_t* mask_tuples, const uint8_t mac_key_le[16],
+                            int use_zero_input_as_data, uint8_t* out_share, int64_t* bad_index,
+                            uint32_t flags, void* stream);
+int amph_mask_input_json(amph_ctx* ctx, const amph_odo_b64* mask_odos, int n_parties, size_t words,
+                         const uint8_t* secrets, size_t n_secrets, char* out_text, size_t out_cap,
+                         int64_t* first_fail, int64_t* bad_char, uint32_t flags, void* stream);
+
 /* ---- Beaver open exchange wire format --------------------------------------
  * MultiplicationExchangeObject.interimValues, the FactorPair list each party
  * sends its partners (amphora-common/.../MultiplicationExchangeObject.java:

@@ -390,6 +390,28 @@ inline std::vector<std::string> maskSecretText(const SecretShareUtil& util, cons
   return out;
 }
 
+// maskSecretText with the records framed: the "data" array text of the
+// MaskedInput body ([{"value":"..."},...]), one launch of amph_mask_input_json.
+inline std::string maskSecretDataText(const SecretShareUtil& util, const std::vector<u128>& secret,
+                                      const std::vector<OdoText>& maskOdos) {
+  std::vector<amph_odo_b64> v;
+  for (auto& o : maskOdos) v.push_back(o.view());
+  const size_t W = maskOdos.empty() ? 0 : wordsOfBase64(maskOdos[0].f[0]);
+  std::vector<u128> s(secret);
+  for (auto& x : s) x %= util.getPrime();
+  Bytes in = packWords(s);
+  std::string text(amph_masked_input_data_chars(s.size()), '\0');
+  int64_t ff = -1, bad = -1;
+  const int st = amph_mask_input_json(util.context().get(), v.data(), (int)v.size(), W, in.data(), s.size(),
+                                      &text[0], text.size(), &ff, &bad, 0, nullptr);
+  if (st == AMPH_E_PARAM && bad >= 0) throw AmphoraClientException(amph_last_error());
+  if (st == AMPH_E_VERIFY) verifyOutputDeliveryText(util, maskOdos);  // throws with the message
+  if (st == AMPH_E_LEN && s.size() > W)
+    throw std::out_of_range("Index " + std::to_string(W) + " out of bounds for length " + std::to_string(W));
+  check(st);
+  return text;
+}
+
 }  // namespace client
 
 namespace service {
@@ -450,6 +472,23 @@ class SecretShareUtil {
     Bytes out(maskedInput.size() * 32);
     check(amph_convert_share(ctx_.get(), m.data(), inputMasks.data(), maskedInput.size(), key,
                              useZeroInputAsData, out.data(), 0, nullptr));
+    return out;
+  }
+
+  // convertToSecretShare on the "data" array text of the MaskedInput body in
+  // Jackson's compact layout (one launch of amph_convert_share_json; any
+  // other layout is the caller's to parse and hand to convertToSecretShare).
+  Bytes convertMaskedInputDataText(const std::string& dataText, const std::string& macKey,
+                                   const Bytes& inputMasks, bool useZeroInputAsData) const {
+    const size_t words = inputMasks.size() / 32;
+    uint8_t key[16];
+    storeLe(fromDecimal(macKey, ctx_.prime()), key);
+    Bytes out(words * 32);
+    int64_t bad = -1;
+    const int st = amph_convert_share_json(ctx_.get(), dataText.data(), dataText.size(), words, inputMasks.data(),
+                                           key, useZeroInputAsData, out.data(), &bad, 0, nullptr);
+    if (st == AMPH_E_LEN || (st == AMPH_E_PARAM && bad >= 0)) throw IllegalArgumentException(amph_last_error());
+    check(st);
     return out;
   }
 
