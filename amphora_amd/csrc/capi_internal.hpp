@@ -1,0 +1,317 @@
+// Internals shared by the units of the C ABI (capi_*.hip): the context, the
+// error and device helpers, the word-array pipeline's types and the buffers
+// of one-shot host calls.  Everything here lives in one namespace of hidden
+// visibility: the library exports only what include/amphora.h declares.
+//
+// Host-pointer calls stream the word arrays through the device in batches
+// (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
+// copy-in stream, the kernel runs on the kernel stream, the outputs come back
+// DtoH on the copy-out stream; three device-side slots let batch k+1's copies
+// overlap batch k's kernel and batch k-1's copy out (run_batched).  Verify
+// failures are reported per batch into a device array of first-fail words,
+// read back once at the end.  Device-pointer calls (AMPH_F_DEVICE) launch
+// straight onto the caller's stream.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <initializer_list>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include <atomic>
+#include <memory>
+#include <thread>
+
+#include "../../include/amphora.h"
+#include "host_stream.hpp"
+#include "kernels.hpp"
+
+namespace capi __attribute__((visibility("hidden"))) {
+using amph::Fp;
+using amph::W4;
+
+// The thread-locals stay private to the unit that defines them and are
+// reached through functions: a constant-initialised extern thread_local of
+// hidden visibility is read through a wrapper whose init hook the linker
+// leaves unresolved, and the first access from another unit jumps to null.
+int fail(int status, const std::string& msg);
+const std::string& last_error();   // what fail() recorded on this thread
+void drop_launch_timing();         // forget a pending amph_time_next_launch
+int hip_fail(hipError_t e, const char* what);
+
+#define HIP_TRY(expr)                                   \
+  do {                                                  \
+    hipError_t e_ = (expr);                             \
+    if (e_ != hipSuccess) return hip_fail(e_, #expr);   \
+  } while (0)
+
+// The context's device for this thread's next HIP calls: hipSetDevice only
+// when the thread's current device differs (hipGetDevice reads thread-local
+// state; the set is what a thread's first HIP call pays for).
+hipError_t use_device(int device);
+
+typedef unsigned __int128 u128;
+
+inline u128 ld128(const uint8_t* b) {
+  uint64_t lo, hi;
+  std::memcpy(&lo, b, 8);
+  std::memcpy(&hi, b + 8, 8);
+  return ((u128)hi << 64) | lo;
+}
+
+inline W4 w4_of(u128 x) {
+  return W4{{(uint32_t)x, (uint32_t)(x >> 32), (uint32_t)(x >> 64), (uint32_t)(x >> 96)}};
+}
+
+inline u128 u128_of(const W4& w) {
+  return ((u128)w.v[3] << 96) | ((u128)w.v[2] << 64) | ((u128)w.v[1] << 32) | w.v[0];
+}
+
+inline std::string dec(u128 x) {
+  if (x == 0) return "0";
+  char buf[48];
+  int n = 0;
+  while (x) {
+    buf[n++] = (char)('0' + (int)(x % 10));
+    x /= 10;
+  }
+  std::string s(buf, n);
+  std::reverse(s.begin(), s.end());
+  return s;
+}
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+}  // namespace capi
+using namespace capi;  // this header is for the capi_*.hip units only
+
+struct amph_ctx {
+  int device = 0;
+  Fp f{};
+  u128 p = 0, r = 0, rinv = 0;
+  std::mutex mu;
+  size_t batch_words = (size_t)4 << 20;
+  int grid_cap = 0;
+  int block = 0;  // 0 = by size (block_for)
+  // host-pointer path: kSlots batches in flight, one stream each
+  static constexpr int kSlots = 3;
+  struct Slot {
+    DevBuf dev;
+    amph::PinnedBuf hin, hout;
+    hipEvent_t in_done = nullptr, k_done = nullptr, out_done = nullptr;
+    bool busy = false;  // hout holds outputs not yet copied to the caller
+    bool used = false;  // the slot has a batch in this call (its events are live)
+    size_t base = 0, cnt = 0;
+  };
+  hipStream_t streams[kSlots] = {};  // host path: HtoD, kernels, DtoH
+  Slot slots[kSlots];
+  std::vector<amph_ctx*> sub;  // amph_ctx_create_multi: one context per device
+  // a sub-context's own long-lived thread (run_sharded posts its shards here)
+  std::unique_ptr<amph::DeviceWorker> worker;
+  DevBuf ff;  // per-batch first-fail words (host path)
+  DevBuf tail;  // small scratch for the partial last unit of codec calls
+  DevBuf wire;  // host-mode staging of the wire-text calls (texts, secrets, outputs, verdicts)
+  DevBuf xstage;  // host-mode staging of the exchange codec calls
+  DevBuf xdev;    // device-mode scan scratch of the exchange codec calls
+  hipEvent_t xdev_done = nullptr;  // the last device-mode exchange call's kernels
+  // small host calls (run_small): one page-locked arena the kernels read and
+  // write in place, and device verdict words kept at kNoFail between calls
+  size_t small_bytes = (size_t)2 << 20;
+  amph::PinnedBuf small;
+  DevBuf small_ff;
+  bool small_ff_dirty = true;
+  std::unique_ptr<amph::CopyPool> pool;
+  // party sessions' device buffers, kept after amph_party_free for the next
+  // session: a server runs one session per request, and hipMalloc / hipFree of
+  // its gigabytes cost tens of microseconds per buffer (hipFree synchronises
+  // the device) -- best fit, at most kPartyPoolMax buffers, freed with the context
+  std::vector<DevBuf> party_pool;
+  size_t pool_cap_bytes = (size_t)32 << 30;  // AMPH_PARTY_POOL_BYTES
+  std::atomic<uint64_t> launches{0};      // amph_ctx_stats
+  std::atomic<uint64_t> worker_tasks{0};
+};
+
+namespace capi __attribute__((visibility("hidden"))) {
+
+// a context allocation that frees the pooled party-session buffers and tries
+// once more when memory runs out (capi_ctx.hip)
+size_t pool_bytes(const amph_ctx* c);
+hipError_t dev_ensure(amph_ctx* c, DevBuf& b, size_t bytes);
+u128 mulmod_host(const amph_ctx* c, u128 a, u128 b);  // a < p
+amph::LaunchCfg cfg(amph_ctx* c, hipStream_t s, size_t words);
+inline int check_ctx(amph_ctx* c) { return c ? AMPH_OK : fail(AMPH_E_PARAM, "null context"); }
+
+// ---- word-array calls (capi_pipeline.hip) --------------------------------------
+// A word-array call is described by its input and output arrays, each with a
+// per-word byte size; the kernel launcher receives device pointers of one
+// batch (host mode) or the caller's own (AMPH_F_DEVICE).
+struct WordArray {
+  uint8_t* host;                          // the caller's pointer; only outputs are written through it
+  size_t bytes_per_word;
+  // AMPH_F_DEVICE: 16 for word arrays (read and written as 16-byte vectors,
+  // global_load/store_dwordx4), 8 for 24-character base64 records (8-byte
+  // vectors), 0 for the 4-byte sign words, which are not checked
+  int dev_align = 16;
+  bool out = false;
+  size_t base = 0;                        // words into the array where this call starts
+  const amph_host_array* io = nullptr;    // AMPH_F_HOST_IO: the callbacks (host unused)
+};
+inline WordArray arr_in(const void* p, size_t bytes_per_word, int dev_align = 16, size_t base = 0) {
+  return WordArray{(uint8_t*)const_cast<void*>(p), bytes_per_word, dev_align, false, base};
+}
+inline WordArray arr_out(void* p, size_t bytes_per_word, int dev_align = 16) {
+  return WordArray{(uint8_t*)p, bytes_per_word, dev_align, true};
+}
+typedef std::vector<WordArray> WordArrays;
+typedef std::vector<const uint4*> DevIn;
+typedef std::vector<uint4*> DevOut;
+// The launch of one batch -- called once per batch (host mode) or once (device
+// mode) -- as a non-owning reference to the entry point's callable, which
+// outlives the call: the pipeline is ordinary functions compiled once.
+class Launch {
+ public:
+  template <class F>
+  Launch(const F& f)
+      : f_(&f), call_([](const void* f, const DevIn& din, const DevOut& dout, size_t cnt, unsigned long long* ff,
+                         const amph::LaunchCfg& lc) { return (*(const F*)f)(din, dout, cnt, ff, lc); }) {}
+  hipError_t operator()(const DevIn& din, const DevOut& dout, size_t cnt, unsigned long long* ff,
+                        const amph::LaunchCfg& lc) const {
+    return call_(f_, din, dout, cnt, ff, lc);
+  }
+
+ private:
+  const void* f_;
+  hipError_t (*call_)(const void*, const DevIn&, const DevOut&, size_t, unsigned long long*, const amph::LaunchCfg&);
+};
+
+// AMPH_F_HOST_IO for the calling thread's current ABI call: set by the entry
+// point (HostIoScope), turned into WordArray::io by run_batched before any
+// work leaves this thread.
+struct HostIoScope {
+  explicit HostIoScope(uint32_t flags);
+  ~HostIoScope();
+};
+
+// Entry of a call that accepts AMPH_F_HOST_IO / one that refuses it.
+#define AMPH_HOST_IO_ENTRY(flags)                                                      \
+  if (((flags) & AMPH_F_HOST_IO) && ((flags) & AMPH_F_DEVICE))                         \
+    return fail(AMPH_E_PARAM, "AMPH_F_HOST_IO and AMPH_F_DEVICE exclude each other");  \
+  HostIoScope host_io_scope_(flags)
+#define AMPH_NO_HOST_IO(flags) \
+  if ((flags) & AMPH_F_HOST_IO) return fail(AMPH_E_PARAM, "AMPH_F_HOST_IO is not accepted by this call")
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Device-pointer word arrays are read and written as 16-byte vectors
+// (global_load/store_dwordx4), so every one must be 16-byte aligned.
+int check_dev_words(std::initializer_list<const void*> ptrs);
+// device-mode first-fail: reset to the sentinel on the caller's stream,
+// unless the caller accumulates (AMPH_F_ACCUMULATE: min-combine into it)
+int reset_ff_dev(int64_t* ff, uint32_t flags, hipStream_t s);
+
+// Host mode of a word-array call: host-io descriptors, then a multi-device
+// context's shards, then a small call, then the batched pipeline.
+int run_batched(amph_ctx* c, size_t words, const WordArrays& ins, const WordArrays& outs, bool with_ff,
+                int64_t* first_fail, const Launch& launch, size_t ff_scale = 1);
+
+// One word-array call in either mode; `arrays` lists inputs and outputs in the
+// order device mode checks their alignment, `launch` sees the inputs as din[]
+// and the outputs as dout[] in that order.
+//   AMPH_F_DEVICE: the alignment checks come before the device is selected (a
+// caller without a GPU gets AMPH_E_PARAM for a misaligned pointer), then the
+// verdict word is reset and `launch` runs once over the caller's pointers on
+// the caller's stream -- no context mutex; a failure is reported as `kernel`.
+//   Host mode: under the context mutex, run_batched.
+int run_words(amph_ctx* c, size_t words, const WordArrays& arrays, bool with_ff, int64_t* first_fail,
+              uint32_t flags, void* stream, const char* kernel, const Launch& launch);
+
+// ---- one-shot host calls (capi_pipeline.hip) -----------------------------------
+// Results of a one-shot host call: wait for the stream, then copy with
+// blocking hipMemcpy (kPageableRule, above read_back's definition).
+struct ReadBack {
+  void* dst;
+  const void* src;
+  size_t bytes;
+};
+hipError_t read_back(hipStream_t s, std::initializer_list<ReadBack> copies);
+
+// the context's own stream k (host mode), created on first use
+int host_stream(amph_ctx* c, int k, hipStream_t* s);
+bool small_call(const amph_ctx* c, size_t bytes);
+// device bytes of arrays carved by Stager::take
+size_t carve_bytes(std::initializer_list<size_t> sizes);
+
+// The buffers of a one-shot host call (one launch, no batching): run_small,
+// the wire-text calls and the exchange codec.  Small: the page-locked arena
+// (capi_pipeline.hip), plain memcpy in and out, the context's device verdict words
+// (kept at kNoFail between calls), one synchronisation.  Staged: everything
+// carved from one per-context device buffer (grown with hipMalloc, held under
+// the context mutex), each input copied with a blocking hipMemcpy while the
+// context's stream is idle (kPageableRule) and the results read back after
+// the kernel.  Two earlier forms of the staged path failed:
+//   * stream-ordered hipMallocAsync staging with pageable hipMemcpyAsync: in
+//     a fresh process the first wire-text call intermittently saw the first
+//     text unit unwritten;
+//   * two contexts on one device calling at the same time got overlapping
+//     hipMallocAsync buffers: each party's exchange text came back empty or
+//     overwritten (tools/c1_native, two party threads).
+struct Stager {
+  amph_ctx* c = nullptr;
+  hipStream_t s = nullptr;
+  bool small = false;
+  int n_ff = 0;
+  unsigned long long* fl = nullptr;  // the device verdict words (staged: after arm)
+  uint8_t *base = nullptr, *dev_base = nullptr;
+  size_t off = 0;
+  // `bytes` of arena when small (plus 256 for the verdict words at its head);
+  // dev_bytes of *dev: the scratch of a small call, everything of a staged one
+  int begin(amph_ctx* ctx, hipStream_t stream, bool use_small, size_t bytes, int verdict_words,
+            DevBuf* dev = nullptr, size_t dev_bytes = 0, const char* what = "");
+  uint8_t* take(size_t bytes) {
+    uint8_t* p = base + off;
+    off += align256(bytes ? bytes : 16);
+    return p;
+  }
+  // the call's device-only scratch (at most one): never in the arena
+  void* scratch(size_t bytes) { return small ? dev_base : take(bytes); }
+  // one word the kernel itself writes for the host (a call without verdict
+  // words): straight into the arena head, or a staged word
+  unsigned long long* result_word();
+  hipError_t put(void* dst, const void* src, size_t bytes);
+  // once, before the launch: a staged call's verdict words, reset on the stream
+  int arm();
+  // after the launch: the verdict words into v (small: to the arena head by
+  // one copy kernel -- none without verdict words -- and ONE synchronisation)
+  // and `outs` to the caller
+  int finish(int64_t* v, std::initializer_list<ReadBack> outs);
+  // outputs a call copies only once it has looked at the verdict
+  int fetch(std::initializer_list<ReadBack> outs);
+  int launch_failed(hipError_t e, const char* what);
+};
+
+// the verdict word of an exchange decode (`pairs` FactorPairs expected in
+// `len` characters) as the call's status and message (capi_text.hip)
+int decode_status(int64_t bad, size_t len, size_t pairs, int64_t* bad_index);
+
+}  // namespace capi

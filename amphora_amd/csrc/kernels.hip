@@ -907,7 +907,7 @@ hipError_t launch_stream_probe(const OdoSet& odo, int n, size_t words, const uin
 }
 
 namespace {
-// Small host calls (capi.hip run_small): the verdict words the kernels
+// Small host calls (run_small): the verdict words the kernels
 // atomicMin'd into device memory go to the page-locked staging arena with
 // plain vector stores, and are reset to kNoFail for the next call.
 __global__ void k_take_words(unsigned long long* dev, unsigned long long* host, int n) {
@@ -920,7 +920,7 @@ __global__ void k_take_words(unsigned long long* dev, unsigned long long* host, 
 }  // namespace
 
 namespace {
-// Device-mode party session (capi.hip amph_party_finish_b64_dev): if any
+// Device-mode party session (amph_party_finish_b64_dev): if any
 // partner text's verdict word reports a failure, the five base64 fields are
 // made unusable -- their first unit becomes "!!!!", which no base64 decoder
 // accepts -- so a response sent without checking the verdicts cannot carry
@@ -945,7 +945,7 @@ hipError_t launch_take_words(unsigned long long* dev, unsigned long long* host, 
   return hipGetLastError();
 }
 
-// Ragged-party tail (capi.hip, ragged_*): the verdict of a one-word call over
+// Ragged-party tail (ragged_*): the verdict of a one-word call over
 // word `base` min-combined into the whole call's first-fail word.
 __global__ void k_ff_merge(unsigned long long* ff, const unsigned long long* tail, unsigned long long base) {
   if (threadIdx.x == 0) {

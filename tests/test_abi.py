@@ -114,6 +114,93 @@ def test_param_validation_before_any_device_work(native):
         assert L.amph_strerror(code)
 
 
+def _device_mode_table(native):
+    """The 13 per-word entry points in device mode over fake addresses: per
+    entry its arrays in the order the library checks them -- (name, kind) with
+    kind "w" (16-byte word array), "r" (24-byte base64 records, 8-byte
+    aligned) or "n" (4-byte sign words, never checked) -- and a call taking
+    {name: address}."""
+    L = native._lib.lib
+    DEV, W, n = native._lib.AMPH_F_DEVICE, 4, 2
+    ff = ctypes.c_int64(0)  # host word: every case fails before first_fail is looked at
+    key = native._lib.le16(5)
+    fields = ["%s%d" % (f, j) for j in range(n) for f in "yrvwu"]
+
+    def odos(a):
+        arr = (native._lib._AmphOdo * n)()
+        for j in range(n):
+            arr[j] = native._lib._AmphOdo(*[a["%s%d" % (f, j)] for f in "yrvwu"], 16 * W)
+        return arr
+
+    def vec(a, stem):
+        return (ctypes.c_void_p * n)(*[a["%s%d" % (stem, j)] for j in range(n)])
+
+    mags = [("mag%d" % j, "w") for j in range(n)]
+    negs = [("neg%d" % j, "n") for j in range(n)]
+    w = lambda *names: [(x, "w") for x in names]
+    return [
+        ("amph_recombine_verify", w(*fields, "out"),
+         lambda c, a: L.amph_recombine_verify(c, odos(a), n, a["out"], ctypes.byref(ff), DEV, None)),
+        ("amph_recombine", w("s0", "s1", "out"),
+         lambda c, a: L.amph_recombine(c, vec(a, "s"), n, 16 * W, a["out"], DEV, None)),
+        ("amph_verify", w("y", "r", "u", "v", "w"),
+         lambda c, a: L.amph_verify(c, a["y"], a["r"], a["u"], a["v"], a["w"], W, ctypes.byref(ff), DEV, None)),
+        ("amph_convert_share", w("masked", "tuples", "out"),
+         lambda c, a: L.amph_convert_share(c, a["masked"], a["tuples"], W, key, 0, a["out"], DEV, None)),
+        ("amph_odo_pre", w("share", "masks", "triples", "oy", "orr", "ov", "omag") + [("oneg", "n")],
+         lambda c, a: L.amph_odo_pre(c, a["share"], 16, a["masks"], a["triples"], W, a["oy"], a["orr"], a["ov"],
+                                     a["omag"], a["oneg"], DEV, None)),
+        ("amph_open_diffs", mags + w("out") + negs,
+         lambda c, a: L.amph_open_diffs(c, vec(a, "mag"), vec(a, "neg"), n, 2 * W, a["out"], DEV, None)),
+        ("amph_odo_post", w("opened", "triples", "ow", "ou"),
+         lambda c, a: L.amph_odo_post(c, a["opened"], a["triples"], W, 1, a["ow"], a["ou"], DEV, None)),
+        ("amph_open_post", mags + w("triples", "ow", "ou") + negs,
+         lambda c, a: L.amph_open_post(c, vec(a, "mag"), vec(a, "neg"), n, a["triples"], W, 1, a["ow"], a["ou"],
+                                       DEV, None)),
+        ("amph_to_gfp", w("in", "out"), lambda c, a: L.amph_to_gfp(c, a["in"], W, a["out"], DEV, None)),
+        ("amph_from_gfp", w("in", "out"), lambda c, a: L.amph_from_gfp(c, a["in"], W, a["out"], DEV, None)),
+        ("amph_mask_words", w("secrets", "masks", "out"),
+         lambda c, a: L.amph_mask_words(c, a["secrets"], a["masks"], W, a["out"], DEV, None)),
+        ("amph_base64_encode_words", [("words16", "w"), ("out24", "r")],
+         lambda c, a: L.amph_base64_encode_words(c, a["words16"], W, a["out24"], DEV, None)),
+        ("amph_base64_decode_words", [("out16", "w"), ("in24", "r")],
+         lambda c, a: L.amph_base64_decode_words(c, a["in24"], W, a["out16"], ctypes.byref(ff), DEV, None)),
+    ]
+
+
+def test_device_mode_alignment_checks_come_before_the_device(native):
+    """Each device-mode word array must be 16-byte aligned and each base64
+    record array 8-byte aligned; the 4-byte sign arrays are not checked.  A
+    misaligned pointer is AMPH_E_PARAM before the library selects a device:
+    the addresses are fake and nothing here launches.  Where there is no GPU
+    the aligned call then fails at the next step, selecting the device."""
+    import torch
+    L, lib = native._lib.lib, native._lib
+    c = native.Context(P, R, RINV)
+    table = _device_mode_table(native)
+    assert len(table) == 13
+    text = {"w": b"16-byte aligned", "r": b"8-byte aligned"}
+    for name, arrays, call in table:
+        good = {a: 0x1000 + 0x100 * i for i, (a, _) in enumerate(arrays)}
+        for a, kind in arrays:  # the sign arrays sit at 4 mod 16 throughout
+            if kind == "n":
+                good[a] += 4
+        for a, kind in arrays:
+            if kind == "n":
+                continue
+            bad = dict(good)
+            bad[a] += 8 if kind == "w" else 4  # 0x..08 for words, 0x..04 for records
+            assert call(c._h, bad) == lib.AMPH_E_PARAM, (name, a)
+            assert text[kind] in L.amph_last_error(), (name, a, L.amph_last_error())
+        # arrays are checked in the listed order: the first misaligned one is reported
+        every = {a: good[a] + (0 if k == "n" else 8 if k == "w" else 4) for a, k in arrays}
+        assert call(c._h, every) == lib.AMPH_E_PARAM, name
+        assert text[arrays[0][1]] in L.amph_last_error(), (name, L.amph_last_error())
+        # all checks passed (sign arrays at 0x..04 included): selecting the device comes next
+        if not torch.cuda.is_available():
+            assert call(c._h, good) == lib.AMPH_E_HIP, (name, L.amph_last_error())
+
+
 def test_multi_device_context_validation(native):
     """amph_ctx_create_multi: argument checks and device count (no GPU work)."""
     L = native._lib.lib

@@ -1,6 +1,6 @@
 """BASELINE config C5 at its size: 256 Mi words x 3 parties streamed from
 page-locked host memory through the GPU in 4 Mi-word batches (the 3-slot
-HtoD / kernel / DtoH pipeline of run_batched, capi.hip), through the two
+HtoD / kernel / DtoH pipeline of run_batched, capi_pipeline.hip), through the two
 host-pointer calls the client makes -- createSecret's verify + mask
 (amph_mask_input, DefaultAmphoraClient.java:150-160) and getSecret's
 recombine + verify (amph_recombine_verify, :206-217,476-505).

@@ -586,6 +586,63 @@ def test_device_arrays_must_be_aligned(ctx, torch):
         ctx.base64_decode_words(rec)
 
 
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("W", [1, 65, 1025])  # one lane, a wave + 1, a 1024-thread block + 1
+def test_per_word_calls_in_both_modes(ctx, F, torch, n, W):
+    """The per-word calls no other test runs on device buffers -- recombine,
+    verify, to_gfp, from_gfp, mask_words, base64_decode_words: host mode
+    against the oracle (C for recombine / verify, Python for the codecs),
+    device mode bit-equal to host mode."""
+    import base64
+    spdz = O.MpSpdzIntegrationUtils(P, R, RINV)
+    odos, _ = F.synth_odos(seed=900 + n, n=n, W=W, fault_index=W // 2)
+    f5 = [np.ascontiguousarray(F.recombine([o[k] for o in odos])) for k in range(5)]  # y r v w u
+    shares = [o[0] for o in odos]
+    y = ctx.recombine(shares)
+    assert np.array_equal(y, f5[0])
+    assert np.array_equal(host(ctx.recombine([dev(torch, s) for s in shares])), y)
+    yv, r, v, w, u = f5
+    assert ctx.verify(yv, r, u, v, w) == W // 2
+    assert ff_dev(ctx.verify(*[dev(torch, a) for a in (yv, r, u, v, w)])) == W // 2
+    x = F.synth_words(seed=910 + n, count=W, mont=False)
+    m = F.synth_words(seed=920 + n, count=W, mont=False)
+    xs = [int.from_bytes(a.tobytes(), "little") for a in x]
+    ms = [int.from_bytes(a.tobytes(), "little") for a in m]
+    g = ctx.to_gfp(x)
+    assert [bytes(a) for a in g] == [spdz.to_gfp(a % P) for a in xs]
+    assert np.array_equal(host(ctx.to_gfp(dev(torch, x))), g)
+    back = ctx.from_gfp(g)
+    assert [int.from_bytes(a.tobytes(), "little") for a in back] == [a % P for a in xs]
+    assert np.array_equal(host(ctx.from_gfp(dev(torch, g))), back)
+    mw = ctx.mask_words(x, m)
+    assert [bytes(a) for a in mw] == [spdz.to_gfp((a - b) % P) for a, b in zip(xs, ms)]
+    assert np.array_equal(host(ctx.mask_words(dev(torch, x), dev(torch, m))), mw)
+    rec = np.frombuffer(b"".join(base64.b64encode(a.tobytes()) for a in x), np.uint8).reshape(W, 24).copy()
+    assert np.array_equal(ctx.base64_decode_words(rec), x)
+    dx, bad = ctx.base64_decode_words(dev(torch, rec))
+    assert ff_dev(bad) == -1 and np.array_equal(host(dx), x)
+
+
+def test_device_mode_needs_a_verdict_word(ctx, torch):
+    """Device mode reports into the caller's device word: a null first_fail /
+    bad_index is AMPH_E_PARAM ("first_fail is required"), nothing is launched."""
+    import amphora_amd as A
+    L, DEVICE = A._lib.lib, A._lib.AMPH_F_DEVICE
+    w = [torch.zeros((1, 16), dtype=torch.uint8, device="cuda") for _ in range(6)]
+    rec = torch.zeros((1, 24), dtype=torch.uint8, device="cuda")
+    p = [t.data_ptr() for t in w]
+    arr, _keep = ctx._odo_structs([tuple(w[:5])])
+    calls = {
+        "amph_verify": lambda: L.amph_verify(ctx._h, *p[:5], 1, None, DEVICE, None),
+        "amph_recombine_verify": lambda: L.amph_recombine_verify(ctx._h, arr, 1, p[5], None, DEVICE, None),
+        "amph_base64_decode_words": lambda: L.amph_base64_decode_words(ctx._h, rec.data_ptr(), 1, p[5], None,
+                                                                        DEVICE, None),
+    }
+    for name, call in calls.items():
+        assert call() == A._lib.AMPH_E_PARAM, name
+        assert b"first_fail is required" in L.amph_last_error(), name
+
+
 def test_stream_probe_pattern(ctx, F):
     """amph_stream_probe (bench.py's same-pattern ceiling kernel) reads every
     array K_MASK reads: its output is the XOR of all of them."""

@@ -1,8 +1,9 @@
-"""The host-copy ordering rule of libamphora_hip (kPageableRule, capi.hip):
+"""The host-copy ordering rule of libamphora_hip (kPageableRule, capi_pipeline.hip):
 hipMemcpyAsync only with page-locked host memory; pageable memory moves with
 a blocking hipMemcpy once the context stream is idle.
 
-* CPU: a static check of capi.hip -- every hipMemcpyAsync with a host
+* CPU: a static check of the C ABI's units (capi_*.hip and their internal
+  header) -- every hipMemcpyAsync with a host
   operand sits in the batched pipeline (run_batched_impl), whose host
   operands are page-locked (the caller's registered buffer, or the slot's
   pinned staging buffer); device-to-device async copies and stream-ordered
@@ -23,7 +24,9 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CAPI = os.path.join(ROOT, "amphora_amd", "csrc", "capi.hip")
+CSRC = os.path.join(ROOT, "amphora_amd", "csrc")
+CAPI = [os.path.join(CSRC, f) for f in ("capi_internal.hpp", "capi_ctx.hip", "capi_pipeline.hip", "capi_words.hip",
+                                        "capi_text.hip", "capi_party.hip")]
 
 
 def _function_spans(src: str):
@@ -41,7 +44,8 @@ def _function_spans(src: str):
 
 
 def test_async_copies_only_in_the_pinned_pipeline():
-    src = open(CAPI).read()
+    assert sorted(f for f in os.listdir(CSRC) if f.startswith("capi")) == sorted(map(os.path.basename, CAPI))
+    src = "\n".join(open(f).read() for f in CAPI)
     code = re.sub(r"//[^\n]*", "", src)  # comments may name the call
     spans = _function_spans(code)
     calls = [m for m in re.finditer(r"\bhipMemcpy(?:2D)?Async\s*\(([^;]*)\);", code)]
@@ -57,8 +61,9 @@ def test_async_copies_only_in_the_pinned_pipeline():
     body = next(code[a:b] for n, a, b in spans if n == "run_batched_impl")
     # host operands: the caller's buffer only when it is page-locked, else the slot's pinned
     # buffer (always for AMPH_F_HOST_IO arrays, which are callbacks, not memory)
-    assert "in_pinned[k] = !ins[k].io && amph::is_pinned_host(ins[k].host)" in body
-    assert "out_pinned[k] = !outs[k].io && amph::is_pinned_host(outs[k].host)" in body
+    # (one loop plans the inputs and the outputs alike)
+    assert "pinned[k] = !v[k].io && amph::is_pinned_host(v[k].host)" in body
+    assert "plan(ins, in_pinned, hin_bytes)" in body and "plan(outs, out_pinned, hout_bytes)" in body
     # stream-ordered allocation: only the device-mode ragged tail's one-word staging
     for m in re.finditer(r"\bhipMallocAsync\s*\(", code):
         owner = [n for n, a, b in spans if a <= m.start() <= b]
