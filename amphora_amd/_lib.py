@@ -73,6 +73,10 @@ def _load():
     L.amph_build_id.restype = C.c_char_p
     L.amph_recombine_verify.argtypes = [vp, vp, i32, vp, i64p, u32, vp]
     L.amph_mask_input.argtypes = [vp, vp, i32, vp, sz, vp, i64p, u32, vp]
+    L.amph_recombine_verify_packed.argtypes = [vp, vp, i32, vp, sz, vp, vp, u32, vp]
+    L.amph_mask_input_packed.argtypes = [vp, vp, i32, vp, sz, vp, vp, vp, u32, vp]
+    L.amph_recombine_verify_batch.argtypes = [vp, vp, i32, sz, C.POINTER(vp), i64p, u32]
+    L.amph_mask_input_batch.argtypes = [vp, vp, i32, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), i64p, u32]
     L.amph_recombine.argtypes = [vp, C.POINTER(vp), i32, sz, vp, u32, vp]
     L.amph_recombine_object.argtypes = [vp, C.POINTER(vp), i32, C.POINTER(sz), vp, u32, vp]
     L.amph_verify.argtypes = [vp, vp, vp, vp, vp, vp, sz, i64p, u32, vp]
@@ -160,6 +164,8 @@ def check_build_id() -> str:
 EXPORTED = ["amph_ctx_create", "amph_ctx_create_multi", "amph_ctx_device_count",
             "amph_ctx_destroy", "amph_ctx_device", "amph_ctx_set_batch_words", "amph_ctx_stats", "amph_strerror",
             "amph_last_error", "amph_version", "amph_build_id", "amph_recombine_verify", "amph_mask_input",
+            "amph_recombine_verify_packed", "amph_mask_input_packed", "amph_recombine_verify_batch",
+            "amph_mask_input_batch",
             "amph_recombine", "amph_recombine_object", "amph_verify", "amph_verify_message", "amph_mask_words", "amph_mask_word_host",
             "amph_to_gfp", "amph_from_gfp", "amph_convert_share", "amph_odo_pre",
             "amph_open_diffs", "amph_odo_post", "amph_open_post", "amph_synth_odos", "amph_synth_words",
@@ -383,6 +389,98 @@ class Context:
         self._check(lib.amph_mask_input(self._h, arr, len(mask_odos), _ptr(s), s.shape[0],
                                         _ptr(out), ffp, flags, stream), allow_verify=True)
         return out, self._ff_value(ff)
+
+    # -- many secrets in one call (include/amphora.h, "many secrets in one call") --
+    def _packed(self, masked, odos, offsets, secrets16, out, first_fail, accumulate):
+        arr, views = self._odo_structs(odos)
+        s = words_view(secrets16) if masked else None
+        like = views[0][0]
+        flags, stream = self._mode(s, *[f for v in views for f in v])
+        T = arr[0].nbytes // 16
+        out = self._out(like, (T, 16), out)
+        if flags & AMPH_F_DEVICE:
+            import torch
+            if not _is_dev(offsets):
+                offsets = torch.as_tensor(np.ascontiguousarray(offsets, dtype=np.uint64).view(np.int64)).to(like.device)
+            if offsets.element_size() != 8 or not offsets.is_contiguous():
+                raise ValueError("offsets must be a contiguous 8-byte integer tensor")
+            K = max(0, offsets.numel() - 1)
+            if first_fail is None:
+                first_fail = torch.empty(K, dtype=torch.int64, device=like.device)
+                accumulate = False
+            elif first_fail.numel() != K or first_fail.dtype != torch.int64 or not first_fail.is_cuda:
+                raise ValueError("first_fail must be an int64 device tensor with one entry per object")
+            if accumulate:
+                flags |= AMPH_F_ACCUMULATE
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            K = max(0, offsets.size - 1)
+            first_fail = np.full(K, -1, dtype=np.int64)
+        if masked:
+            _need(s.shape[0] == T, "the packed form takes one secret per input mask word")
+            st = lib.amph_mask_input_packed(self._h, arr, len(odos), _ptr(offsets), K, _ptr(s), _ptr(out),
+                                            _ptr(first_fail), flags, stream)
+        else:
+            st = lib.amph_recombine_verify_packed(self._h, arr, len(odos), _ptr(offsets), K, _ptr(out),
+                                                  _ptr(first_fail), flags, stream)
+        self._check(st, allow_verify=True)
+        return out, first_fail
+
+    def recombine_verify_packed(self, odos, offsets, out=None, first_fail=None, accumulate=False):
+        """K secrets in one launch.  odos: list over parties of (y, r, v, w, u),
+        each the concatenation of the K objects' words; offsets: K + 1 word
+        offsets (numpy, or a device tensor beside device fields).  Returns
+        (secrets (T, 16), first_fail): host -- int64[K] of -1 / the object's
+        smallest failing local word; device -- an int64[K] tensor of
+        AMPH_NO_FAILURE / index (pass first_fail with accumulate=True to
+        min-combine into an earlier call's verdicts)."""
+        return self._packed(False, odos, offsets, None, out, first_fail, accumulate)
+
+    def mask_input_packed(self, mask_odos, offsets, secrets16, out=None, first_fail=None, accumulate=False):
+        """recombine_verify_packed over Input Mask ODOs fused with maskInput:
+        one secret per mask word, packed on the same offsets."""
+        return self._packed(True, mask_odos, offsets, secrets16, out, first_fail, accumulate)
+
+    def _batch(self, masked, objects, secrets):
+        K = len(objects)
+        n = len(objects[0]) if K else 1
+        arr = (_AmphOdo * max(1, K * n))()
+        keep, outs = [], []
+        for o, obj in enumerate(objects):
+            if len(obj) != n:
+                raise ValueError("every object needs the same number of parties")
+            a, views = self._odo_structs(obj)
+            if any(_is_dev(f) for v in views for f in v):
+                raise ValueError("the batch calls take host arrays")
+            keep.append(views)
+            for j in range(n):
+                arr[o * n + j] = a[j]
+            outs.append(np.empty((a[0].nbytes // 16, 16), dtype=np.uint8))
+        ff = np.full(K, -1, dtype=np.int64)
+        ffp = ff.ctypes.data_as(C.POINTER(C.c_int64))
+        outp = (C.c_void_p * max(1, K))(*[x.ctypes.data for x in outs])
+        if masked:
+            if len(secrets) != K:
+                raise ValueError("one secrets array per object")
+            sv = [words_view(x) for x in secrets]
+            sp = (C.c_void_p * max(1, K))(*[x.ctypes.data for x in sv])
+            ns = (C.c_size_t * max(1, K))(*[x.shape[0] for x in sv])
+            st = lib.amph_mask_input_batch(self._h, arr, n, K, sp, ns, outp, ffp, 0)
+        else:
+            st = lib.amph_recombine_verify_batch(self._h, arr, n, K, outp, ffp, 0)
+        self._check(st, allow_verify=True)
+        return outs, ff
+
+    def recombine_verify_batch(self, objects):
+        """objects: list over secrets of recombine_verify's `odos` (host arrays).
+        One launch; returns (list of (W_o, 16) secrets, int64[K] of -1 / the
+        object's first failing word) -- per object what recombine_verify gives."""
+        return self._batch(False, objects, None)
+
+    def mask_input_batch(self, objects, secrets):
+        """mask_input for K secrets at once; secrets[o] must hold exactly as many
+        words as object o has input masks (AMPH_E_LEN otherwise)."""
+        return self._batch(True, objects, secrets)
 
     def recombine(self, shares):
         vs = [words_view(s) for s in shares]

@@ -186,6 +186,81 @@ def create_masked_input(util: SecretShareUtil, secret: Secret,
     return MaskedInput(secret.secret_id, MaskedInputWords(masked), list(secret.tags))
 
 
+# ---- many secrets per launch ------------------------------------------------------
+# The reference client has no multi-secret method: K getSecret / createSecret
+# calls each return their own secret or throw their own exception.  The batch
+# functions keep that contract -- one entry per secret, the value or the
+# exception the single function would raise -- over ONE launch
+# (amph_recombine_verify_batch / amph_mask_input_batch).
+
+def _outcome(fn, *args):
+    try:
+        return fn(*args)
+    except Exception as e:  # the caller gets it as this secret's entry
+        return e
+
+
+def _regular(arrays, n_parties: int) -> bool:
+    """All 5 n fields of one byte length: what the gathered ABI calls take.
+    Anything else (ragged parties, another party count) keeps the single
+    call's semantics and exceptions by going through the single call."""
+    if len(arrays) != n_parties or n_parties == 0:
+        return False
+    b0 = _lib.byte_len(arrays[0][0])
+    return all(len(a) == 5 and all(_lib.byte_len(f) == b0 for f in a) for a in arrays)
+
+
+def _batch_outcomes(util, arrays_list, regular, run, finish, single):
+    out = [None] * len(arrays_list)
+    idx = [o for o, r in enumerate(regular) if r]
+    if idx:
+        words, ff = run(idx)
+        for k, o in enumerate(idx):
+            if ff[k] >= 0:
+                out[o] = _outcome(_raise_for, util, arrays_list[o], int(ff[k]))
+            else:
+                out[o] = finish(o, words[k])
+    for o, r in enumerate(regular):
+        if not r:
+            out[o] = _outcome(single, o)
+    return out
+
+
+def verify_output_delivery_objects_batch(util: SecretShareUtil,
+                                         list_of_odo_lists: Sequence[Sequence[OutputDeliveryObject]]):
+    """verify_output_delivery_objects for K secrets in one launch.  Returns a
+    list with one entry per secret: the canonical secrets (List[int]), or the
+    exception the single function would raise for that secret (for a MAC
+    failure, IntegrityVerificationException with the reference's message)."""
+    arrays_list = [_odo_arrays(odos) for odos in list_of_odo_lists]
+    n = next((len(a) for a in arrays_list if len(a)), 0)
+    regular = [_regular(a, n) for a in arrays_list]
+    return _batch_outcomes(
+        util, arrays_list, regular,
+        lambda idx: util.context.recombine_verify_batch([arrays_list[o] for o in idx]),
+        lambda o, y: unpack(y),
+        lambda o: verify_output_delivery_objects(util, list_of_odo_lists[o]))
+
+
+def create_masked_inputs(util: SecretShareUtil, secrets: Sequence[Secret],
+                         list_of_mask_odo_lists: Sequence[Sequence[OutputDeliveryObject]]):
+    """create_masked_input for K secrets in one launch: one entry per secret,
+    the MaskedInput or the exception create_masked_input would raise.  A
+    secret whose word count differs from its mask count goes through the
+    single call (which verifies the masks before it reports the length)."""
+    if len(secrets) != len(list_of_mask_odo_lists):
+        raise ValueError("one list of Input Mask ODOs per secret")
+    arrays_list = [_odo_arrays(odos) for odos in list_of_mask_odo_lists]
+    n = next((len(a) for a in arrays_list if len(a)), 0)
+    regular = [_regular(a, n) and secrets[o].size() == _words(a) for o, a in enumerate(arrays_list)]
+    return _batch_outcomes(
+        util, arrays_list, regular,
+        lambda idx: util.context.mask_input_batch([arrays_list[o] for o in idx],
+                                                  [pack(secrets[o].data, util.prime) for o in idx]),
+        lambda o, m: MaskedInput(secrets[o].secret_id, MaskedInputWords(m), list(secrets[o].tags)),
+        lambda o: create_masked_input(util, secrets[o], list_of_mask_odo_lists[o]))
+
+
 def _texts_and_words(bodies):
     """Field texts of every party's body and the word count.  A malformed
     body -- a field that is not a whole number of 16-byte words, or fields of

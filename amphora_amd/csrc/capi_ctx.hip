@@ -247,6 +247,10 @@ void amph_ctx_destroy(amph_ctx* c) {
     (void)hipEventDestroy(c->xdev_done);
   }
   c->xdev.release();
+  if (c->seg.p) {
+    (void)use_device(c->device);
+    c->seg.release();
+  }
   if (!c->party_pool.empty()) {
     (void)use_device(c->device);
     for (DevBuf& b : c->party_pool) b.release();

@@ -18,6 +18,7 @@
 #include <initializer_list>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -140,6 +141,7 @@ struct amph_ctx {
   size_t small_bytes = (size_t)2 << 20;
   amph::PinnedBuf small;
   DevBuf small_ff;
+  DevBuf seg;  // packed host calls (run_packed): the device offsets table, then the verdict array
   bool small_ff_dirty = true;
   std::unique_ptr<amph::CopyPool> pool;
   // party sessions' device buffers, kept after amph_party_free for the next
@@ -245,6 +247,23 @@ int run_batched(amph_ctx* c, size_t words, const WordArrays& ins, const WordArra
 //   Host mode: under the context mutex, run_batched.
 int run_words(amph_ctx* c, size_t words, const WordArrays& arrays, bool with_ff, int64_t* first_fail,
               uint32_t flags, void* stream, const char* kernel, const Launch& launch);
+
+// ---- packed calls (capi_pipeline.hip) --------------------------------------------
+// The launch of one batch of a packed (segmented) call: Launch's arguments
+// with the batch's first global word, the device copy of the offsets table
+// and the call's device verdict array (one word per object).
+typedef std::function<hipError_t(const DevIn& din, const DevOut& dout, size_t cnt, size_t base,
+                                 const uint64_t* offsets, unsigned long long* ff, const amph::LaunchCfg& lc)>
+    SegLaunch;
+// Host mode of a packed call, under the context mutex: `offsets` (validated by
+// the caller, n_objects + 1 host words, offsets[n_objects] = words) goes to
+// the device once, the verdict array stays there across the call's batches
+// and is read back once.  A call that fits the small-call arena runs there
+// (table and verdicts included), any other through the batched pipeline.
+// first_fail[o] = -1 or object o's smallest failing local index;
+// AMPH_E_VERIFY (amph_last_error names the first failing object) if any failed.
+int run_packed(amph_ctx* c, size_t words, const WordArrays& ins, const WordArrays& outs, const uint64_t* offsets,
+               size_t n_objects, int64_t* first_fail, const SegLaunch& launch);
 
 // ---- one-shot host calls (capi_pipeline.hip) -----------------------------------
 // Results of a one-shot host call: wait for the stream, then copy with

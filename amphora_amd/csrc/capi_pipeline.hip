@@ -200,7 +200,9 @@ int run_batched_impl(amph_ctx* c, size_t words, const WordArrays& ins, const Wor
     HIP_TRY(hipStreamWaitEvent(s_k, sl.in_done, 0));
     if (sl.used) HIP_TRY(hipStreamWaitEvent(s_k, sl.out_done, 0));  // outputs copied out
     unsigned long long* ff = with_ff ? (unsigned long long*)c->ff.p + b : nullptr;
-    hipError_t e = launch(din, dout, cnt, ff, cfg(c, s_k, cnt));
+    amph::LaunchCfg lc = cfg(c, s_k, cnt);
+    lc.base = base;
+    hipError_t e = launch(din, dout, cnt, ff, lc);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     HIP_TRY(hipEventRecord(sl.k_done, s_k));
     // the slot's staging buffer still holds the previous batch's outputs
@@ -388,6 +390,20 @@ size_t call_bytes(size_t words, const WordArrays& ins, const WordArrays& outs) {
 // An error part-way through leaves earlier batches' copies in flight (into
 // the caller's page-locked buffers, or the slots): wait for them before
 // returning, so nothing writes caller memory after the call has returned.
+namespace {
+int run_pipeline(amph_ctx* c, size_t words, const WordArrays& ins, const WordArrays& outs, bool with_ff,
+                 int64_t* first_fail, const Launch& launch, size_t ff_scale) {
+  const int rc = run_batched_impl(c, words, ins, outs, with_ff, first_fail, launch, ff_scale);
+  if (rc != AMPH_OK && rc != AMPH_E_VERIFY) {
+    for (int s = 0; s < amph_ctx::kSlots; ++s) {
+      if (c->streams[s]) (void)hipStreamSynchronize(c->streams[s]);
+      c->slots[s].busy = false;
+    }
+  }
+  return rc;
+}
+}  // namespace
+
 int run_batched(amph_ctx* c, size_t words, const WordArrays& ins, const WordArrays& outs, bool with_ff,
                 int64_t* first_fail, const Launch& launch, size_t ff_scale) {
   if (g_host_io) {  // the entry point's AMPH_F_HOST_IO: the pointers are descriptors
@@ -407,14 +423,88 @@ int run_batched(amph_ctx* c, size_t words, const WordArrays& ins, const WordArra
   if (!c->sub.empty()) return run_sharded(c, words, ins, outs, with_ff, first_fail, launch, ff_scale);
   const size_t bytes = call_bytes(words, ins, outs);
   if (small_call(c, bytes)) return run_small(c, words, ins, outs, with_ff, first_fail, launch, bytes);
-  const int rc = run_batched_impl(c, words, ins, outs, with_ff, first_fail, launch, ff_scale);
-  if (rc != AMPH_OK && rc != AMPH_E_VERIFY) {
-    for (int s = 0; s < amph_ctx::kSlots; ++s) {
-      if (c->streams[s]) (void)hipStreamSynchronize(c->streams[s]);
-      c->slots[s].busy = false;
-    }
+  return run_pipeline(c, words, ins, outs, with_ff, first_fail, launch, ff_scale);
+}
+
+// ---- packed calls ----------------------------------------------------------------
+// The verdicts of a packed call live in a device array of one word per object
+// (c->seg, after the offsets table) that every batch's kernel min-combines
+// into; the pipeline's own per-batch first-fail words are not used.
+namespace {
+// the verdict array as the caller's first_fail entries and the call's status
+int packed_status(const unsigned long long* v, size_t n_objects, int64_t* first_fail) {
+  size_t failed = 0, first = 0;
+  for (size_t o = 0; o < n_objects; ++o) {
+    const bool bad = v[o] != amph::kNoFail;
+    if (bad && !failed++) first = o;
+    if (first_fail) first_fail[o] = bad ? (int64_t)v[o] : -1;
   }
-  return rc;
+  if (!failed) return AMPH_OK;
+  return fail(AMPH_E_VERIFY, "Verification of secret has failed: object " + std::to_string(first) + " at word " +
+                                 std::to_string(v[first]) + " (" + std::to_string(failed) + " of " +
+                                 std::to_string(n_objects) + " objects failed)");
+}
+
+// run_small for a packed call: the table sits in the arena too (only a
+// failing lane reads it), the verdict array in device memory (atomics) and
+// comes to the arena by a copy kernel before the call's ONE synchronisation.
+int run_packed_small(amph_ctx* c, size_t words, const WordArrays& ins, const WordArrays& outs,
+                     const uint64_t* offsets, size_t n_objects, int64_t* first_fail, const SegLaunch& launch,
+                     size_t bytes) {
+  hipStream_t s;
+  if (int st = host_stream(c, 1, &s)) return st;
+  Stager h;
+  if (int st = h.begin(c, s, true, bytes, 0, &c->seg, align256(8 * n_objects), "verdict array")) return st;
+  DevIn din;
+  DevOut dout;
+  for (const WordArray& x : ins) {
+    uint8_t* p = h.take(words * x.bytes_per_word);
+    if (amph::run_copy(copy_in(x, 0, words, p))) return io_failed();
+    din.push_back((const uint4*)p);
+  }
+  for (const WordArray& x : outs) dout.push_back((uint4*)h.take(words * x.bytes_per_word));
+  uint64_t* tab = (uint64_t*)h.take(8 * (n_objects + 1));
+  std::memcpy(tab, offsets, 8 * (n_objects + 1));
+  unsigned long long* hv = (unsigned long long*)h.take(8 * n_objects);
+  unsigned long long* dv = (unsigned long long*)c->seg.p;
+  HIP_TRY(hipMemsetAsync(dv, 0x7F, 8 * n_objects, s));
+  hipError_t e = launch(din, dout, words, 0, tab, dv, cfg(c, s, words));
+  if (e != hipSuccess) return h.launch_failed(e, "kernel launch");
+  e = amph::launch_take_array(dv, hv, n_objects, s);
+  if (e != hipSuccess) return h.launch_failed(e, "verdict copy");
+  e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return hip_fail(e, "small-call synchronise");
+  for (size_t k = 0; k < outs.size(); ++k)
+    if (amph::run_copy(copy_out(outs[k], 0, words, dout[k]))) return io_failed();
+  return packed_status(hv, n_objects, first_fail);
+}
+}  // namespace
+
+int run_packed(amph_ctx* c, size_t words, const WordArrays& ins, const WordArrays& outs, const uint64_t* offsets,
+               size_t n_objects, int64_t* first_fail, const SegLaunch& launch) {
+  if (n_objects == 0) return AMPH_OK;
+  if (words == 0) {  // nothing to verify: every object reads "verified"
+    for (size_t o = 0; first_fail && o < n_objects; ++o) first_fail[o] = -1;
+    return AMPH_OK;
+  }
+  HIP_TRY(use_device(c->device));
+  const size_t tab_bytes = align256(8 * (n_objects + 1)), ff_bytes = align256(8 * n_objects);
+  const size_t bytes = call_bytes(words, ins, outs) + tab_bytes + ff_bytes;
+  if (small_call(c, bytes)) return run_packed_small(c, words, ins, outs, offsets, n_objects, first_fail, launch, bytes);
+  hipStream_t s_k;
+  if (int st = host_stream(c, 1, &s_k)) return st;
+  if (dev_ensure(c, c->seg, tab_bytes + ff_bytes) != hipSuccess) return fail(AMPH_E_NOMEM, "offsets table");
+  const uint64_t* tab = (const uint64_t*)c->seg.p;
+  unsigned long long* dv = (unsigned long long*)((uint8_t*)c->seg.p + tab_bytes);
+  // kPageableRule: the context's streams are idle between calls
+  HIP_TRY(hipMemcpy(c->seg.p, offsets, 8 * (n_objects + 1), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(dv, 0x7F, 8 * n_objects, s_k));
+  auto batch = [&](const DevIn& din, const DevOut& dout, size_t cnt, unsigned long long*,
+                   const amph::LaunchCfg& lc) { return launch(din, dout, cnt, lc.base, tab, dv, lc); };
+  if (int st = run_pipeline(c, words, ins, outs, false, nullptr, batch, 1)) return st;
+  std::vector<unsigned long long> v(n_objects);  // the pipeline has synchronised the kernel stream
+  HIP_TRY(hipMemcpy(v.data(), dv, 8 * n_objects, hipMemcpyDeviceToHost));
+  return packed_status(v.data(), n_objects, first_fail);
 }
 
 // Multi-device context: contiguous shards of ceil(words / ndev), one thread

@@ -1,8 +1,10 @@
 // C ABI of libamphora_hip (declared in include/amphora.h): the per-word entry
 // points -- each one launch, written once for both modes (run_words,
 // capi_internal.hpp) -- the ragged last word of recombineObject's party
-// arrays, the synthetic data generators and the stream probe.
+// arrays, the packed and gathered many-secret calls, the synthetic data
+// generators and the stream probe.
 #include "capi_internal.hpp"
+#include "seglookup.hpp"
 
 namespace {
 // recombineObject's word count and ragged party arrays (client
@@ -225,9 +227,196 @@ int ragged_odo_call(amph_ctx* c, const amph_odo* odos, int n, size_t W, bool mas
   return v >= 0 ? AMPH_E_VERIFY : AMPH_OK;
 }
 
+// ---- packed and gathered calls (amph_*_packed, amph_*_batch) --------------------
+// Packed parties have no ragged form: every party holds all T words.
+int packed_words(const amph_odo* odos, int n, size_t* words) {
+  if (!odos || n < 1 || n > AMPH_MAX_PARTIES)
+    return fail(AMPH_E_PARAM, "n_parties must be in [1, 16] with a non-null ODO array");
+  for (int j = 0; j < n; ++j)
+    if (odos[j].nbytes != odos[0].nbytes || odos[j].nbytes % AMPH_WORD_WIDTH)
+      return fail(AMPH_E_LEN, "packed ODOs: party " + std::to_string(j) + " holds " +
+                                  std::to_string(odos[j].nbytes) + " bytes, party 0 " +
+                                  std::to_string(odos[0].nbytes) + " (equal multiples of 16 required)");
+  *words = odos[0].nbytes / AMPH_WORD_WIDTH;
+  for (int j = 0; j < n; ++j)
+    if (*words && (!odos[j].secret_shares || !odos[j].r_shares || !odos[j].v_shares || !odos[j].w_shares ||
+                   !odos[j].u_shares))
+      return fail(AMPH_E_PARAM, "null ODO field");
+  return AMPH_OK;
+}
+
+// a host offsets table: offsets[0] = 0, nondecreasing, offsets[n_objects] = words
+int check_offsets(const uint64_t* offsets, size_t n_objects, size_t words) {
+  if (!offsets) return fail(AMPH_E_PARAM, "null offsets table");
+  if (offsets[0] != 0) return fail(AMPH_E_PARAM, "offsets[0] must be 0");
+  for (size_t o = 0; o < n_objects; ++o)
+    if (offsets[o + 1] < offsets[o])
+      return fail(AMPH_E_PARAM, "offsets must not decrease (entry " + std::to_string(o + 1) + ")");
+  if (offsets[n_objects] != words)
+    return fail(AMPH_E_PARAM, "offsets[n_objects] = " + std::to_string(offsets[n_objects]) +
+                                  " must equal the ODO word count " + std::to_string(words));
+  return AMPH_OK;
+}
+
+// Both packed calls: `masked` = false runs K_RV, true K_MASK (secrets != null).
+int packed_call(amph_ctx* c, const amph_odo* odos, int n, const uint64_t* offsets, size_t n_objects, bool masked,
+                const uint8_t* secrets, uint8_t* out, int64_t* first_fail, uint32_t flags, void* stream) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  AMPH_NO_HOST_IO(flags);
+  if (n_objects == 0) return AMPH_OK;
+  size_t T;
+  if (int st = packed_words(odos, n, &T)) return st;
+  if (!offsets || !first_fail) return fail(AMPH_E_PARAM, "null offsets table or first_fail array");
+  if (T && (!out || (masked && !secrets))) return fail(AMPH_E_PARAM, masked ? "null secrets/output" : "null output");
+  if (!c->sub.empty()) c = c->sub[0];  // a multi-device context runs packed calls on its first device
+  const auto launch = [&](const DevIn& din, const DevOut& dout, size_t cnt, size_t base, const uint64_t* tab,
+                          unsigned long long* ff, const amph::LaunchCfg& lc) {
+    const amph::OdoSet set = odo_set(din.data(), n);
+    return masked ? amph::launch_mask_input_seg(set, n, cnt, din[5 * n], dout[0], ff, tab, n_objects, base, c->f, lc)
+                  : amph::launch_recombine_verify_seg(set, n, cnt, dout[0], ff, tab, n_objects, base, c->f, lc);
+  };
+  if (flags & AMPH_F_DEVICE) {
+    if (int st = check_dev_odos(odos, n)) return st;
+    if (int st = check_dev_words({secrets, out})) return st;
+    if (((uintptr_t)offsets | (uintptr_t)first_fail) & 7)
+      return fail(AMPH_E_PARAM, "device offsets and first_fail arrays must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(use_device(c->device));
+    if (!(flags & AMPH_F_ACCUMULATE)) HIP_TRY(hipMemsetAsync(first_fail, 0x7F, 8 * n_objects, s));
+    DevIn din;
+    for (int k = 0; k < 5; ++k)
+      for (int j = 0; j < n; ++j) din.push_back((const uint4*)odo_field(odos[j], k));
+    if (masked) din.push_back((const uint4*)secrets);
+    const hipError_t e = launch(din, DevOut{(uint4*)out}, T, 0, offsets, (unsigned long long*)first_fail,
+                                cfg(c, s, T));
+    return e == hipSuccess ? AMPH_OK : hip_fail(e, masked ? "k_mask_seg" : "k_rv_seg");
+  }
+  if (int st = check_offsets(offsets, n_objects, T)) return st;
+  WordArrays ins = odo_arrays(odos, n);
+  if (masked) ins.push_back(arr_in(secrets, 16));
+  std::lock_guard<std::mutex> g(c->mu);
+  return run_packed(c, T, ins, {arr_out(out, 16)}, offsets, n_objects, first_fail, launch);
+}
+
+// One packed array of a gathered call as an amph_host_array: its read / write
+// walk the objects' separate pieces (piece[o] holds object o's words), so the
+// pipeline's staging copies gather and scatter in the same pass that moves
+// the bytes into page-locked memory.
+struct Gather {
+  amph_host_array a{};
+  std::vector<uint8_t*> piece;
+  const uint64_t* offsets = nullptr;
+  size_t n_objects = 0;
+};
+int gather_rw(const amph_host_array* a, size_t off, size_t bytes, uint8_t* buf, bool write) {
+  const Gather* g = (const Gather*)a->user;
+  size_t o = amph::seg_find(g->offsets, g->n_objects, off / AMPH_WORD_WIDTH);
+  while (bytes) {
+    const size_t lo = AMPH_WORD_WIDTH * g->offsets[o], hi = AMPH_WORD_WIDTH * g->offsets[o + 1];
+    if (off >= hi) {  // an empty object, or this one is done
+      ++o;
+      continue;
+    }
+    const size_t nb = std::min(bytes, hi - off);
+    if (write) std::memcpy(g->piece[o] + (off - lo), buf, nb);
+    else std::memcpy(buf, g->piece[o] + (off - lo), nb);
+    buf += nb, off += nb, bytes -= nb;
+  }
+  return 0;
+}
+void gather_init(Gather& g, const std::vector<uint64_t>& offsets) {
+  g.offsets = offsets.data();
+  g.n_objects = offsets.size() - 1;
+  g.piece.resize(g.n_objects);
+  g.a.user = &g;
+  g.a.read = [](const amph_host_array* a, size_t off, size_t bytes, void* dst) {
+    return gather_rw(a, off, bytes, (uint8_t*)dst, false);
+  };
+  g.a.write = [](const amph_host_array* a, size_t off, size_t bytes, const void* src) {
+    return gather_rw(a, off, bytes, (uint8_t*)const_cast<void*>(src), true);
+  };
+}
+WordArray gather_array(const Gather& g, bool out) { return WordArray{nullptr, 16, 16, out, 0, &g.a}; }
+
+// Both gathered calls: odos[o * n + j] is party j's ODO of object o.
+int batch_call(amph_ctx* c, const amph_odo* odos, int n, size_t n_objects, bool masked,
+               const uint8_t* const* secrets, const size_t* n_secrets, uint8_t* const* out, int64_t* first_fail,
+               uint32_t flags) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  if (flags) return fail(AMPH_E_PARAM, "the gathered batch calls take host memory only (flags must be 0)");
+  if (n_objects == 0) return AMPH_OK;
+  if (!odos || n < 1 || n > AMPH_MAX_PARTIES)
+    return fail(AMPH_E_PARAM, "n_parties must be in [1, 16] with a non-null ODO array");
+  if (!out || !first_fail || (masked && (!secrets || !n_secrets)))
+    return fail(AMPH_E_PARAM, "null pointer array or first_fail array");
+  std::vector<uint64_t> offsets(n_objects + 1, 0);
+  for (size_t o = 0; o < n_objects; ++o) {
+    const amph_odo* po = odos + o * (size_t)n;
+    for (int j = 1; j < n; ++j)
+      if (po[j].nbytes != po[0].nbytes)
+        return fail(AMPH_E_LEN, "object " + std::to_string(o) + ": The provided shares must be of the same length");
+    const size_t w = po[0].nbytes / AMPH_WORD_WIDTH;
+    if (masked && n_secrets[o] != w)
+      return fail(AMPH_E_LEN, "object " + std::to_string(o) + ": " + std::to_string(n_secrets[o]) +
+                                  " secret words for " + std::to_string(w) + " input masks");
+    for (int j = 0; j < n; ++j)
+      if (w && (!po[j].secret_shares || !po[j].r_shares || !po[j].v_shares || !po[j].w_shares || !po[j].u_shares))
+        return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null ODO field");
+    if (w && (!out[o] || (masked && !secrets[o])))
+      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null secrets/output");
+    offsets[o + 1] = offsets[o] + w;
+  }
+  const size_t T = offsets[n_objects];
+  std::vector<Gather> arrays(5 * (size_t)n + (masked ? 2 : 1));
+  for (Gather& g : arrays) gather_init(g, offsets);
+  for (size_t o = 0; o < n_objects; ++o) {
+    for (int k = 0; k < 5; ++k)
+      for (int j = 0; j < n; ++j)
+        arrays[k * n + j].piece[o] = const_cast<uint8_t*>(odo_field(odos[o * (size_t)n + j], k));
+    if (masked) arrays[5 * n].piece[o] = const_cast<uint8_t*>(secrets[o]);
+    arrays.back().piece[o] = out[o];
+  }
+  WordArrays ins;
+  for (size_t k = 0; k + 1 < arrays.size(); ++k) ins.push_back(gather_array(arrays[k], false));
+  if (!c->sub.empty()) c = c->sub[0];
+  std::lock_guard<std::mutex> g(c->mu);
+  return run_packed(c, T, ins, {gather_array(arrays.back(), true)}, offsets.data(), n_objects, first_fail,
+                    [&](const DevIn& din, const DevOut& dout, size_t cnt, size_t base, const uint64_t* tab,
+                        unsigned long long* ff, const amph::LaunchCfg& lc) {
+                      const amph::OdoSet set = odo_set(din.data(), n);
+                      return masked ? amph::launch_mask_input_seg(set, n, cnt, din[5 * n], dout[0], ff, tab,
+                                                                  n_objects, base, c->f, lc)
+                                    : amph::launch_recombine_verify_seg(set, n, cnt, dout[0], ff, tab, n_objects,
+                                                                        base, c->f, lc);
+                    });
+}
+
 }  // namespace
 
 extern "C" {
+
+int amph_recombine_verify_packed(amph_ctx* c, const amph_odo* odos, int n, const uint64_t* offsets,
+                                 size_t n_objects, uint8_t* out_secrets, int64_t* first_fail, uint32_t flags,
+                                 void* stream) {
+  return packed_call(c, odos, n, offsets, n_objects, false, nullptr, out_secrets, first_fail, flags, stream);
+}
+
+int amph_mask_input_packed(amph_ctx* c, const amph_odo* odos, int n, const uint64_t* offsets, size_t n_objects,
+                           const uint8_t* secrets, uint8_t* out_masked, int64_t* first_fail, uint32_t flags,
+                           void* stream) {
+  return packed_call(c, odos, n, offsets, n_objects, true, secrets, out_masked, first_fail, flags, stream);
+}
+
+int amph_recombine_verify_batch(amph_ctx* c, const amph_odo* odos, int n, size_t n_objects,
+                                uint8_t* const* out_secrets, int64_t* first_fail, uint32_t flags) {
+  return batch_call(c, odos, n, n_objects, false, nullptr, nullptr, out_secrets, first_fail, flags);
+}
+
+int amph_mask_input_batch(amph_ctx* c, const amph_odo* odos, int n, size_t n_objects,
+                          const uint8_t* const* secrets, const size_t* n_secrets, uint8_t* const* out_masked,
+                          int64_t* first_fail, uint32_t flags) {
+  return batch_call(c, odos, n, n_objects, true, secrets, n_secrets, out_masked, first_fail, flags);
+}
 
 int amph_recombine_verify(amph_ctx* c, const amph_odo* odos, int n, uint8_t* out_secrets,
                           int64_t* first_fail, uint32_t flags, void* stream) {

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "seglookup.hpp"
 
 namespace amph {
 
@@ -84,6 +85,37 @@ __device__ __forceinline__ void report_fail(bool bad, size_t i, unsigned long lo
   if (m != 0ULL) {
     const int lane = __lane_id();
     if (lane == __ffsll((long long)m) - 1) atomicMin(ff, (unsigned long long)i);
+  }
+}
+
+// Failure path of the segmented kernels (k_rv_seg / k_mask_seg): global word
+// gi failed; the object that owns it (seg_find) gets gi's local index
+// min-combined into its verdict word.  gap = the distance to the next lower
+// failing lane of this wave, 0 for none: a wave's lanes hold consecutive
+// words, so that lane's word is gi - gap, and when it lies in the same object
+// this lane's index is not the object's smallest and the atomic is skipped.
+// The lowest failing lane of every object in the wave always reports.
+// Inlined into the cold branch: as a real call (noinline) the values live
+// across it moved to callee-saved registers and k_mask_seg at 3 parties went
+// from 64 to 66 VGPRs (7 waves per SIMD); inlined, the branch runs after the
+// store, when the word's registers are dead, and the counts are k_rv's /
+// k_mask's ("Packed calls").
+__device__ __forceinline__ void seg_report(unsigned long long gi, unsigned gap, const uint64_t* offsets,
+                                           size_t n_objects, unsigned long long* ff) {
+  const size_t o = seg_find(offsets, n_objects, gi);
+  const unsigned long long lo = offsets[o];
+  if (gap && gi - gap >= lo) return;
+  atomicMin(ff + o, gi - lo);
+}
+
+// report_fail over a verdict array: no table access unless a word failed.
+__device__ __forceinline__ void report_fail_seg(bool bad, size_t gi, const uint64_t* offsets, size_t n_objects,
+                                                unsigned long long* ff) {
+  const unsigned long long m = __ballot(bad);
+  if (m != 0ULL && bad) {
+    const unsigned long long below = m & ((1ULL << __lane_id()) - 1ULL);
+    const unsigned gap = below ? (unsigned)(__lane_id() - (63 - __clzll((long long)below))) : 0u;
+    seg_report((unsigned long long)gi, gap, offsets, n_objects, ff);
   }
 }
 

@@ -18,6 +18,8 @@
 
 #include <hip/hip_ext.h>
 
+#include <algorithm>
+
 #include "b64.hpp"
 #include "decimal.hpp"
 #include "devio.hpp"
@@ -104,6 +106,41 @@ __global__ __launch_bounds__(kMaxBlock) void k_mask(OdoSet odo, int n, size_t wo
     // VGPRs at 3 parties (8 waves per SIMD: two 1024-lane workgroups per CU)
     st_out(out + i, mod_sub(MASK_SECRET_MUL(w4(s), r2, f), a[0], f));
     report_fail(!ok, i, ff);
+  }
+}
+
+// Segmented forms over a packed layout (kernels.hpp, launch_*_seg): the same
+// loads, arithmetic and stores as k_rv / k_mask; the offsets table is touched
+// only by a lane whose word failed (report_fail_seg).  ibase = the global word
+// of this launch's word 0 (a host batch in the middle of the packed range).
+template <int NP, bool BIG>
+__global__ __launch_bounds__(kMaxBlock) void k_rv_seg(OdoSet odo, int n, size_t words, uint4* out_y,
+                                                  unsigned long long* ff, Fp f, size_t ibase,
+                                                  const uint64_t* offsets, size_t n_objects) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) {
+    W4 a[5];
+    recombine5<NP, BIG>(odo, n, i, f, a);
+    const bool ok = (int)eq(mont_mul(a[0], a[1], f), a[3]) & (int)eq(mont_mul(a[2], a[1], f), a[4]);
+    st_out(out_y + i, redc(a[0], f));
+    report_fail_seg(!ok, ibase + i, offsets, n_objects, ff);
+  }
+}
+
+template <int NP, bool BIG>
+__global__ __launch_bounds__(kMaxBlock) void k_mask_seg(OdoSet odo, int n, size_t words,
+                                                    const uint4* secrets, uint4* out,
+                                                    unsigned long long* ff, Fp f, size_t ibase,
+                                                    const uint64_t* offsets, size_t n_objects) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const W4 r2 = r2_word(f);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) {
+    const uint4 s = ld(secrets + i);
+    W4 a[5];
+    recombine5<NP, BIG>(odo, n, i, f, a);
+    const bool ok = (int)eq(mont_mul(a[0], a[1], f), a[3]) & (int)eq(mont_mul(a[2], a[1], f), a[4]);
+    st_out(out + i, mod_sub(MASK_SECRET_MUL(w4(s), r2, f), a[0], f));
+    report_fail_seg(!ok, ibase + i, offsets, n_objects, ff);
   }
 }
 
@@ -761,6 +798,28 @@ hipError_t launch_mask_input(const OdoSet& odo, int n, size_t words, const uint4
   return hipGetLastError();
 }
 
+hipError_t launch_recombine_verify_seg(const OdoSet& odo, int n, size_t words, uint4* out_y,
+                                       unsigned long long* ff, const uint64_t* offsets, size_t n_objects,
+                                       size_t ibase, const Fp& f, const LaunchCfg& c) {
+  if (words == 0 || n_objects == 0) return hipSuccess;
+  const unsigned g = grid_for(words, c);
+#define L(NP, BIG) AMPH_LAUNCH((k_rv_seg<NP, BIG>), dim3(g), dim3(c.block), c, odo, n, words, out_y, ff, f, ibase, offsets, n_objects)
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+#undef L
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_input_seg(const OdoSet& odo, int n, size_t words, const uint4* secrets, uint4* out,
+                                 unsigned long long* ff, const uint64_t* offsets, size_t n_objects,
+                                 size_t ibase, const Fp& f, const LaunchCfg& c) {
+  if (words == 0 || n_objects == 0) return hipSuccess;
+  const unsigned g = grid_for(words, c);
+#define L(NP, BIG) AMPH_LAUNCH((k_mask_seg<NP, BIG>), dim3(g), dim3(c.block), c, odo, n, words, secrets, out, ff, f, ibase, offsets, n_objects)
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+#undef L
+  return hipGetLastError();
+}
+
 hipError_t launch_recombine(const ShareSet& sh, int n, size_t words, uint4* out, const Fp& f,
                             const LaunchCfg& c) {
   if (words == 0) return hipSuccess;
@@ -936,6 +995,22 @@ __global__ void k_poison_b64(PoisonB64 a) {
 hipError_t launch_poison_b64(const PoisonB64& a, hipStream_t s) {
   if (a.n_bad <= 0 || a.chars < 4) return hipSuccess;
   hipLaunchKernelGGL(k_poison_b64, dim3(1), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+namespace {
+// Packed small host calls: the verdict array (one word per object) from device
+// memory to the page-locked arena with plain vector stores.
+__global__ void k_take_array(const unsigned long long* dev, unsigned long long* host, size_t n) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) host[i] = dev[i];
+}
+}  // namespace
+
+hipError_t launch_take_array(const unsigned long long* dev, unsigned long long* host, size_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const size_t g = std::min<size_t>((n + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_take_array, dim3((unsigned)g), dim3(256), 0, s, dev, host, n);
   return hipGetLastError();
 }
 

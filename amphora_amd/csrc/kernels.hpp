@@ -65,6 +65,7 @@ struct LaunchCfg {
   int block;     // threads per workgroup, multiple of 64, <= kMaxBlock
   hipEvent_t ev_start = nullptr;  // optional: stamped by the kernel dispatch itself
   hipEvent_t ev_stop = nullptr;
+  size_t base = 0;  // host pipeline: the batch's first word within the call (0 elsewhere)
 };
 
 // K_RV: recombine 5 fields over n parties, verify w == y r, u == v r,
@@ -77,6 +78,21 @@ hipError_t launch_recombine_verify(const OdoSet& odo, int n, size_t words, uint4
 hipError_t launch_mask_input(const OdoSet& odo, int n, size_t words, const uint4* secrets,
                              size_t n_secrets, uint4* out_masked, unsigned long long* first_fail,
                              const Fp& f, const LaunchCfg& c);
+
+// Segmented K_RV / K_MASK over a packed layout: every field of every party is
+// the concatenation of n_objects objects' words, object o owning words
+// [offsets[o], offsets[o + 1]) (seglookup.hpp; device table of n_objects + 1
+// words).  first_fail is an array of n_objects words: a failing global word g
+// of object o min-combines g - offsets[o] into first_fail[o].  The launch
+// covers global words [ibase, ibase + words) -- the array pointers are those
+// of word ibase.  One secret per word for the mask form (no verify-only tail).
+hipError_t launch_recombine_verify_seg(const OdoSet& odo, int n, size_t words, uint4* out_y,
+                                       unsigned long long* first_fail, const uint64_t* offsets,
+                                       size_t n_objects, size_t ibase, const Fp& f, const LaunchCfg& c);
+hipError_t launch_mask_input_seg(const OdoSet& odo, int n, size_t words, const uint4* secrets,
+                                 uint4* out_masked, unsigned long long* first_fail,
+                                 const uint64_t* offsets, size_t n_objects, size_t ibase, const Fp& f,
+                                 const LaunchCfg& c);
 
 // recombineObject for one field: canonical sum_j fromGfp(share_j).
 hipError_t launch_recombine(const ShareSet& sh, int n, size_t words, uint4* out, const Fp& f,
@@ -202,6 +218,8 @@ hipError_t launch_mask_json(const TextSet& tx, int n, size_t words, size_t nchar
 // Small host calls: copy n verdict words from device memory to page-locked
 // host memory and reset them to kNoFail (one 64-lane workgroup).
 hipError_t launch_take_words(unsigned long long* dev, unsigned long long* host, int n, hipStream_t s);
+// Packed small host calls: n verdict words (any n) to page-locked host memory.
+hipError_t launch_take_array(const unsigned long long* dev, unsigned long long* host, size_t n, hipStream_t s);
 
 // Device-mode party session: poison the five base64 fields ("!!!!" as their
 // first unit) when any partner verdict word is not kNoFail (one workgroup).

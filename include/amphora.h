@@ -259,6 +259,64 @@ int amph_mask_input(amph_ctx* ctx, const amph_odo* mask_odos, int n_parties,
                     const uint8_t* secrets, size_t n_secrets, uint8_t* out_masked,
                     int64_t* first_fail, uint32_t flags, void* stream);
 
+/* ---- many secrets in one call, one verdict per secret -------------------- */
+/* PACKED form of amph_recombine_verify / amph_mask_input: K objects (secrets)
+ * in one launch, each with its own verdict, as K getSecret / createSecret
+ * calls would give.
+ *   Layout: every field of every party is the concatenation of the objects'
+ *   words, T words in all.  offsets[n_objects + 1] are word offsets:
+ *   offsets[0] = 0, nondecreasing, offsets[n_objects] = T; object o owns words
+ *   [offsets[o], offsets[o + 1]) and may be empty.  odos[j] = party j's five
+ *   packed fields; every party's nbytes must be the same multiple of 16
+ *   (AMPH_E_LEN otherwise: there are no ragged parties here).  out_secrets /
+ *   out_masked are packed on the same offsets (T words); amph_mask_input_packed
+ *   takes one secret per mask word (T LE16 integers), there is no verify-only
+ *   tail.  first_fail has n_objects entries.
+ *   Host mode: the table is checked (AMPH_E_PARAM, nothing launched, when
+ *   offsets[0] != 0, an entry decreases or offsets[n_objects] differs from the
+ *   ODO word count).  first_fail[o] = -1, or the smallest failing word of
+ *   object o counted from the object's first word; the output words are
+ *   written for failed objects too.  Returns AMPH_E_VERIFY if any object
+ *   failed (amph_last_error names the first failing object and how many
+ *   failed).  Small calls use the small-call arena, larger ones the batched
+ *   pipeline; the verdicts stay on the device across batches.
+ *   AMPH_F_DEVICE: offsets and first_fail are device arrays, 8-byte aligned;
+ *   asynchronous on `stream`.  Every first_fail entry is reset to
+ *   AMPH_NO_FAILURE first unless AMPH_F_ACCUMULATE is set (then the entries
+ *   are min-combined).  T = odos[0].nbytes / 16.  The table's contract is the
+ *   CALLER's and is not checked: a table that breaks it may credit a failure
+ *   to the wrong object, but no entry outside first_fail[0, n_objects) is
+ *   ever written (the lookup is bounded by n_objects) -- and the output words
+ *   do not depend on the table.
+ *   AMPH_F_HOST_IO is refused (AMPH_E_PARAM).  A multi-device context runs
+ *   these calls on devices[0], as the exchange codec.  n_objects == 0 returns
+ *   AMPH_OK and launches nothing; T == 0 leaves every verdict "verified". */
+int amph_recombine_verify_packed(amph_ctx* ctx, const amph_odo* odos, int n_parties,
+                                 const uint64_t* offsets, size_t n_objects, uint8_t* out_secrets,
+                                 int64_t* first_fail, uint32_t flags, void* stream);
+int amph_mask_input_packed(amph_ctx* ctx, const amph_odo* mask_odos, int n_parties,
+                           const uint64_t* offsets, size_t n_objects, const uint8_t* secrets,
+                           uint8_t* out_masked, int64_t* first_fail, uint32_t flags, void* stream);
+
+/* GATHER form, host memory only (any flag: AMPH_E_PARAM): one amph_odo per
+ * object per party, odos[o * n_parties + j] = party j's ODO of object o, and
+ * one output (and secrets) array per object.  Object o has
+ * odos[o * n_parties].nbytes / 16 words; every party of an object must have
+ * the same nbytes (AMPH_E_LEN, the message names the object).  The library
+ * gathers the pieces into page-locked staging, runs the packed path once and
+ * scatters the outputs.  Per object, out_secrets[o] / out_masked[o] (also of
+ * a failed object) and first_fail[o] are bit-identical to the single call on
+ * that object alone; the status is the packed form's.
+ * amph_mask_input_batch: n_secrets[o] must EQUAL object o's word count, else
+ * AMPH_E_LEN (object named) before any GPU work -- unlike amph_mask_input,
+ * which verifies the masks first and accepts fewer secrets; a caller who
+ * needs the reference's order for such an object uses the single call. */
+int amph_recombine_verify_batch(amph_ctx* ctx, const amph_odo* odos, int n_parties, size_t n_objects,
+                                uint8_t* const* out_secrets, int64_t* first_fail, uint32_t flags);
+int amph_mask_input_batch(amph_ctx* ctx, const amph_odo* mask_odos, int n_parties, size_t n_objects,
+                          const uint8_t* const* secrets, const size_t* n_secrets,
+                          uint8_t* const* out_masked, int64_t* first_fail, uint32_t flags);
+
 /* recombineObject for one byte[] field: out[i] = sum_j fromGfp(share_j[i]) mod p. */
 int amph_recombine(amph_ctx* ctx, const uint8_t* const* shares, int n_parties, size_t nbytes,
                    uint8_t* out, uint32_t flags, void* stream);

@@ -261,6 +261,23 @@ class SecretShareUtil {
   Context ctx_;
 };
 
+// The reference's IntegrityVerificationException for word ff of one secret's
+// ODOs, its message rendered from the recombined values of that word.
+[[noreturn]] inline void throwVerificationFailure(const SecretShareUtil& util,
+                                                  const std::vector<OutputDeliveryObject>& odos, int64_t ff) {
+  std::vector<u128> f[5];
+  for (int k = 0; k < 5; ++k) {
+    std::vector<Bytes> sh;
+    for (auto& o : odos) {
+      const Bytes& src = k == 0 ? o.getSecretShares() : k == 1 ? o.getRShares() : k == 2 ? o.getVShares()
+                       : k == 3 ? o.getWShares() : o.getUShares();
+      sh.push_back(copyOfRange(src, 16 * ff, 16 * ff + 16));  // a ragged party's word: zero-padded
+    }
+    f[k] = util.recombineObject(sh);
+  }
+  throw IntegrityVerificationException(util.message(f[0][0], f[1][0], f[4][0], f[2][0], f[3][0]));
+}
+
 // DefaultAmphoraClient.verifyOutputDeliveryObjects :476-505 (K_RV)
 inline std::vector<u128> verifyOutputDeliveryObjects(const SecretShareUtil& util,
                                                      const std::vector<OutputDeliveryObject>& odos) {
@@ -271,19 +288,7 @@ inline std::vector<u128> verifyOutputDeliveryObjects(const SecretShareUtil& util
   int64_t ff = -1;
   const int st = amph_recombine_verify(util.context().get(), v.data(), (int)v.size(), out.data(),
                                        &ff, 0, nullptr);
-  if (st == AMPH_E_VERIFY) {
-    std::vector<u128> f[5];
-    for (int k = 0; k < 5; ++k) {
-      std::vector<Bytes> sh;
-      for (auto& o : odos) {
-        const Bytes& src = k == 0 ? o.getSecretShares() : k == 1 ? o.getRShares() : k == 2 ? o.getVShares()
-                         : k == 3 ? o.getWShares() : o.getUShares();
-        sh.push_back(copyOfRange(src, 16 * ff, 16 * ff + 16));  // a ragged party's word: zero-padded
-      }
-      f[k] = util.recombineObject(sh);
-    }
-    throw IntegrityVerificationException(util.message(f[0][0], f[1][0], f[4][0], f[2][0], f[3][0]));
-  }
+  if (st == AMPH_E_VERIFY) throwVerificationFailure(util, odos, ff);
   check(st);
   return unpackWords(out);
 }
@@ -306,6 +311,126 @@ inline std::vector<Bytes> maskSecret(const SecretShareUtil& util, const std::vec
   std::vector<Bytes> words;
   for (size_t i = 0; i < s.size(); ++i) words.emplace_back(out.begin() + 16 * i, out.begin() + 16 * i + 16);
   return words;
+}
+
+// ---- many secrets per launch (amph_recombine_verify_batch / amph_mask_input_batch)
+// The reference client has no multi-secret method; K calls each return their
+// own secret or throw their own exception.  One entry per secret keeps that:
+// the value, or the exception the single call would throw (get() rethrows it).
+template <class T>
+struct Outcome {
+  T value{};
+  std::exception_ptr error;
+  bool ok() const { return !error; }
+  const T& get() const {
+    if (error) std::rethrow_exception(error);
+    return value;
+  }
+};
+
+namespace detail {
+// objects the gathered ABI calls take: `parties` ODOs of one byte length
+inline bool regularObject(const std::vector<OutputDeliveryObject>& odos, size_t parties) {
+  if (odos.size() != parties || parties == 0) return false;
+  for (auto& o : odos)
+    if (o.getSecretShares().size() != odos[0].getSecretShares().size()) return false;
+  return true;
+}
+template <class T, class F>
+inline Outcome<T> outcomeOf(F&& f) {
+  Outcome<T> r;
+  try {
+    r.value = f();
+  } catch (...) {
+    r.error = std::current_exception();
+  }
+  return r;
+}
+}  // namespace detail
+
+// verifyOutputDeliveryObjects for K secrets in one launch.  Ragged objects and
+// objects of another party count go through the single call.
+inline std::vector<Outcome<std::vector<u128>>> verifyOutputDeliveryObjectsBatch(
+    const SecretShareUtil& util, const std::vector<std::vector<OutputDeliveryObject>>& objects) {
+  typedef std::vector<u128> V;
+  std::vector<Outcome<V>> res(objects.size());
+  size_t n = 0;
+  for (auto& o : objects)
+    if (!o.empty() && !n) n = o.size();
+  std::vector<size_t> idx;
+  std::vector<amph_odo> v;
+  std::vector<Bytes> outs;
+  for (size_t o = 0; o < objects.size(); ++o) {
+    if (!detail::regularObject(objects[o], n)) {
+      res[o] = detail::outcomeOf<V>([&] { return verifyOutputDeliveryObjects(util, objects[o]); });
+      continue;
+    }
+    idx.push_back(o);
+    for (auto& p : objects[o]) v.push_back(p.view());
+    outs.emplace_back(objects[o][0].getSecretShares().size() / 16 * 16);
+  }
+  if (idx.empty()) return res;
+  std::vector<uint8_t*> outp;
+  for (auto& b : outs) outp.push_back(b.data());
+  std::vector<int64_t> ff(idx.size(), -1);
+  const int st = amph_recombine_verify_batch(util.context().get(), v.data(), (int)n, idx.size(), outp.data(),
+                                             ff.data(), 0);
+  if (st != AMPH_E_VERIFY) check(st);
+  for (size_t k = 0; k < idx.size(); ++k) {
+    const size_t o = idx[k];
+    if (ff[k] >= 0) res[o] = detail::outcomeOf<V>([&]() -> V { throwVerificationFailure(util, objects[o], ff[k]); });
+    else res[o].value = unpackWords(outs[k]);
+  }
+  return res;
+}
+
+// maskSecret for K secrets in one launch.  A secret whose word count differs
+// from its mask count goes through the single call (which verifies first).
+inline std::vector<Outcome<std::vector<Bytes>>> maskSecrets(
+    const SecretShareUtil& util, const std::vector<std::vector<u128>>& secrets,
+    const std::vector<std::vector<OutputDeliveryObject>>& maskOdos) {
+  typedef std::vector<Bytes> V;
+  if (secrets.size() != maskOdos.size()) throw IllegalArgumentException("one list of Input Mask ODOs per secret");
+  std::vector<Outcome<V>> res(secrets.size());
+  size_t n = 0;
+  for (auto& o : maskOdos)
+    if (!o.empty() && !n) n = o.size();
+  std::vector<size_t> idx, ns;
+  std::vector<amph_odo> v;
+  std::vector<Bytes> ins, outs;
+  for (size_t o = 0; o < secrets.size(); ++o) {
+    if (!detail::regularObject(maskOdos[o], n) ||
+        maskOdos[o][0].getSecretShares().size() / 16 != secrets[o].size()) {
+      res[o] = detail::outcomeOf<V>([&] { return maskSecret(util, secrets[o], maskOdos[o]); });
+      continue;
+    }
+    idx.push_back(o);
+    for (auto& p : maskOdos[o]) v.push_back(p.view());
+    std::vector<u128> s(secrets[o]);
+    for (auto& x : s) x %= util.getPrime();
+    ins.push_back(packWords(s));
+    outs.emplace_back(ins.back().size());
+    ns.push_back(s.size());
+  }
+  if (idx.empty()) return res;
+  std::vector<const uint8_t*> inp;
+  std::vector<uint8_t*> outp;
+  for (auto& b : ins) inp.push_back(b.data());
+  for (auto& b : outs) outp.push_back(b.data());
+  std::vector<int64_t> ff(idx.size(), -1);
+  const int st = amph_mask_input_batch(util.context().get(), v.data(), (int)n, idx.size(), inp.data(), ns.data(),
+                                       outp.data(), ff.data(), 0);
+  if (st != AMPH_E_VERIFY) check(st);
+  for (size_t k = 0; k < idx.size(); ++k) {
+    const size_t o = idx[k];
+    if (ff[k] >= 0) {
+      res[o] = detail::outcomeOf<V>([&]() -> V { throwVerificationFailure(util, maskOdos[o], ff[k]); });
+      continue;
+    }
+    for (size_t i = 0; i < ns[k]; ++i)
+      res[o].value.emplace_back(outs[k].begin() + 16 * i, outs[k].begin() + 16 * i + 16);
+  }
+  return res;
 }
 
 // The five base64 field strings of one party's VerifiableSecretShare /
