@@ -25,6 +25,29 @@ namespace amph {
     default: LAUNCH(0, BIG); break;      \
   }
 
+// !BIG (p < 2^127, a rare configuration) in the kernels that hold every
+// party's five fields at once: canon() is two Montgomery-sized products per
+// input word there, and the forms templated on the larger party counts spill
+// to scratch (K_RV / K_MASK and their segmented forms at 4 parties: 416 bytes
+// per lane; the wire-fused forms at 3 and 4: 96 and 416).  Scratch costs
+// bandwidth and stays allocated to the process's queues after the launch, so
+// those counts take the run-time form, which loads one party at a time and
+// keeps everything in registers (SMALL3: templated up to 3 parties, SMALL2:
+// up to 2).
+#define AMPH_DISPATCH_NP_SMALL3(n, LAUNCH) \
+  switch (n) {                             \
+    case 1: LAUNCH(1, false); break;       \
+    case 2: LAUNCH(2, false); break;       \
+    case 3: LAUNCH(3, false); break;       \
+    default: LAUNCH(0, false); break;      \
+  }
+#define AMPH_DISPATCH_NP_SMALL2(n, LAUNCH) \
+  switch (n) {                             \
+    case 1: LAUNCH(1, false); break;       \
+    case 2: LAUNCH(2, false); break;       \
+    default: LAUNCH(0, false); break;      \
+  }
+
 namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

@@ -226,7 +226,10 @@ __host__ __device__ __forceinline__ W4 mont_mul_v(const W4& a, const W4& b, cons
 }
 
 // Montgomery reduction of a single word: a * 2^-128 mod p (a < 2^128).
-// = fromGfp on a wire word.
+// = fromGfp on a wire word.  (t4 is always 0 here: with a < 2^128 and
+// p < 2^128 each step's value is at most (2^128 - 1 + (2^32 - 1) p) / 2^32
+// < 2^128, so no step carries out of t3.  It is kept so that the loop body
+// reads like mont_mul_cios's reduction half, where the carry is live.)
 __host__ __device__ __forceinline__ W4 redc(const W4& a, const Fp& f) {
   uint32_t t0 = a.v[0], t1 = a.v[1], t2 = a.v[2], t3 = a.v[3], t4 = 0;
 #pragma unroll

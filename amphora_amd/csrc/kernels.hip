@@ -754,7 +754,10 @@ unsigned grid_for(size_t words, const LaunchCfg& c) {
 }
 
 // Dispatch helpers: party count is a template parameter for 1..4 (the
-// configurations Amphora deploys), runtime loop above that.
+// configurations Amphora deploys), runtime loop above that.  Below 2^127
+// (!BIG) k_rv / k_mask and their segmented forms are templated for 1..3 only
+// (AMPH_DISPATCH_NP_SMALL3, devio.hpp: the 4-party form spilled to scratch);
+// the wire kernels (wire.hip) for 1..2.
 
 }  // namespace
 
@@ -763,7 +766,7 @@ hipError_t launch_recombine_verify(const OdoSet& odo, int n, size_t words, uint4
   if (words == 0) return hipSuccess;
   const unsigned g = grid_for(words, c);
 #define L(NP, BIG) AMPH_LAUNCH((k_rv<NP, BIG>), dim3(g), dim3(c.block), c, odo, n, words, out_y, ff, f, (size_t)0)
-  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL3(n, L) }
 #undef L
   return hipGetLastError();
 }
@@ -777,7 +780,7 @@ hipError_t launch_mask_input(const OdoSet& odo, int n, size_t words, const uint4
     LaunchCfg c1 = c;  // timing events bracket both launches when there is a tail
     if (words > n_secrets) c1.ev_stop = nullptr;
 #define L(NP, BIG) AMPH_LAUNCH((k_mask<NP, BIG>), dim3(g), dim3(c.block), c1, odo, n, n_secrets, secrets, out, ff, f)
-    if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+    if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL3(n, L) }
 #undef L
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -792,7 +795,7 @@ hipError_t launch_mask_input(const OdoSet& odo, int n, size_t words, const uint4
     LaunchCfg c2 = c;
     if (n_secrets > 0) c2.ev_start = nullptr;
 #define L(NP, BIG) AMPH_LAUNCH((k_rv<NP, BIG, false>), dim3(g), dim3(c.block), c2, tail, n, tw, (uint4*)nullptr, ff, f, n_secrets)
-    if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+    if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL3(n, L) }
 #undef L
   }
   return hipGetLastError();
@@ -804,7 +807,7 @@ hipError_t launch_recombine_verify_seg(const OdoSet& odo, int n, size_t words, u
   if (words == 0 || n_objects == 0) return hipSuccess;
   const unsigned g = grid_for(words, c);
 #define L(NP, BIG) AMPH_LAUNCH((k_rv_seg<NP, BIG>), dim3(g), dim3(c.block), c, odo, n, words, out_y, ff, f, ibase, offsets, n_objects)
-  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL3(n, L) }
 #undef L
   return hipGetLastError();
 }
@@ -815,7 +818,7 @@ hipError_t launch_mask_input_seg(const OdoSet& odo, int n, size_t words, const u
   if (words == 0 || n_objects == 0) return hipSuccess;
   const unsigned g = grid_for(words, c);
 #define L(NP, BIG) AMPH_LAUNCH((k_mask_seg<NP, BIG>), dim3(g), dim3(c.block), c, odo, n, words, secrets, out, ff, f, ibase, offsets, n_objects)
-  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL3(n, L) }
 #undef L
   return hipGetLastError();
 }

@@ -375,7 +375,7 @@ hipError_t launch_rv_b64(const TextSet& tx, int n, size_t words, size_t nchars, 
   constexpr int BS = kWireBlock;
   const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
 #define L(NP, BIG) AMPH_LAUNCH((k_rv_b64<NP, BIG, BS>), g, dim3(BS), c, tx, n, words, nchars, pad, out_y, ff, bad, f)
-  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
 #undef L
   return hipGetLastError();
 }
@@ -388,7 +388,7 @@ hipError_t launch_mask_b64(const TextSet& tx, int n, size_t words, size_t nchars
   constexpr int BS = kWireBlock;
   const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
 #define L(NP, BIG) AMPH_LAUNCH((k_mask_b64<NP, BIG, BS>), g, dim3(BS), c, tx, n, words, nchars, pad, secrets, n_secrets, out16, out24, ff, bad, f)
-  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
 #undef L
   return hipGetLastError();
 }
@@ -401,7 +401,7 @@ hipError_t launch_mask_json(const TextSet& tx, int n, size_t words, size_t nchar
   constexpr int BS = kWireBlock;
   const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
 #define L(NP, BIG) AMPH_LAUNCH((k_mask_json<NP, BIG, BS>), g, dim3(BS), c, tx, n, words, nchars, pad, secrets, n_secrets, out_text, ff, bad, f)
-  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
 #undef L
   return hipGetLastError();
 }

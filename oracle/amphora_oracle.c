@@ -22,7 +22,8 @@
  *   orc_odo_post          OutputDeliveryService.java:147-152,274-286
  *   orc_recombine_diffs   OutputDeliveryService.java:231-272
  * The third-party codec (mp-spdz-integration 0.2.2, absent) is restated as in
- * oracle/amphora_oracle.py (ENCODING "mont_le").  Requires 2^64 <= p < 2^128.
+ * oracle/amphora_oracle.py (ENCODING "mont_le").  Any odd p with 3 <= p < 2^128
+ * (below 2^64 the reduction is a one-digit short division).
  *
  * Parallelism mirrors the reference's parallelStream over words: OpenMP
  * static schedule over the word index, `nthreads` threads.
@@ -59,6 +60,12 @@ static void st16(uint8_t* b, u128 x) {
 /* 256-bit (4 x 64-bit digits, little-endian) mod p: Knuth algorithm D with
  * 64-bit digits (Hacker's Delight divmnu, n = 2). */
 static u128 mod256(const orc_field* f, const u64 x[4]) {
+  if (f->s < 0) { /* p < 2^64: one-digit divisor, schoolbook short division */
+    const u64 p = (u64)f->p;
+    u64 r = 0;
+    for (int i = 3; i >= 0; --i) r = (u64)((((u128)r << 64) | x[i]) % p);
+    return r;
+  }
   u64 un[5];
   const int s = f->s;
   if (s == 0) {
@@ -147,13 +154,19 @@ int orc_field_init(orc_field* f, const uint8_t p[16], const uint8_t r[16], const
   f->p = ld16(p);
   f->r = ld16(r);
   f->rinv = ld16(rinv);
-  if ((f->p >> 64) == 0 || (f->p & 1) == 0) return -1;
+  if (f->p < 3 || (f->p & 1) == 0) return -1;
   u64 hi = (u64)(f->p >> 64);
-  int s = __builtin_clzll(hi);
-  f->s = s;
-  u128 pn = f->p << s;
-  f->vn[0] = (u64)pn;
-  f->vn[1] = (u64)(pn >> 64);
+  if (hi == 0) { /* one 64-bit digit: algorithm D needs two (mod256's short division) */
+    f->s = -1;
+    f->vn[0] = (u64)f->p;
+    f->vn[1] = 0;
+  } else {
+    int s = __builtin_clzll(hi);
+    f->s = s;
+    u128 pn = f->p << s;
+    f->vn[0] = (u64)pn;
+    f->vn[1] = (u64)(pn >> 64);
+  }
   if (mulmod(f, f->r, f->rinv) != 1) return -2;
   return 0;
 }

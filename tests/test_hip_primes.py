@@ -1,0 +1,449 @@
+"""Every field kernel on every prime of tests/field_cases.py -- the control,
+2^128 - 159 (dot2_redc's second top-limb bit), 2^127 + 29, 2^127 - 1 and
+2^89 - 1 (n0 == 1), primes of two and one limbs, and 3 -- on the edge grid
+E x E of carry-chain operands, bit-exact against the plain Python-int
+reference AND the C oracle (which must agree with each other; the oracle
+itself is pinned on the CPU by tests/test_oracle_primes.py).
+
+This launches the BIG and the !BIG instantiation of every arithmetic kernel
+(K_RV, K_MASK, recombine, verify, the codecs, K_CONV, K_ODO_PRE, open,
+K_ODO_POST, the fused open + post, the wire-fused and segmented kernels, the
+party session, the synthetic inputs), pins the device lowering of
+addc / subc / macc96 (mont_mul_ps runs in the wire kernels and for K_MASK's
+secret product, mont_mul_cios in K_RV: both are compared with the same
+reference), and sends partner diffs with raw magnitudes (>= p, negative zero,
+negative p, 2^128 - 1).  Each test asserts its coverage predicates on the
+inputs (Python ints only) before it calls the library.  Arrays hold at most
+|E|^2 (about 2.5k) words.
+"""
+import base64
+import json
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from oracle import coracle  # noqa: E402
+from tests import field_cases as FC  # noqa: E402
+
+NF = 0x7F7F7F7F7F7F7F7F
+
+
+class Env:
+    def __init__(self, pid):
+        import torch
+        assert torch.cuda.is_available()
+        import amphora_amd as A
+        self.pr = FC.BY_ID[pid]
+        self.ctx = A.Context(self.pr.p, self.pr.r, self.pr.rinv)
+        self.F = coracle.Field(self.pr.p, self.pr.r, self.pr.rinv, threads=4)
+        self._rv = {}
+
+    def rv(self, n):
+        """(rows, the parties' arrays, expected secrets (W, 16)): the Python
+        reference and the C oracle agree, computed once per party count."""
+        if n not in self._rv:
+            rows = FC.odo_rows(self.pr.id, n)
+            odos = FC.odo_arrays(rows)
+            ys, ff = FC.recombine_verify(self.pr, rows.odos)
+            oy, off = self.F.recombine_verify(odos)
+            assert ff == off == -1 and ys == list(rows.ys) == FC.ints(oy)
+            oy.setflags(write=False)
+            self._rv[n] = (rows, odos, oy)
+        return self._rv[n]
+
+    def secrets(self, W):
+        E = FC.edge_words(self.pr.p)
+        return [E[(3 * i + i // len(E)) % len(E)] for i in range(W)]  # raw words, >= p included
+
+
+@pytest.fixture(scope="module", params=FC.PRIME_IDS)
+def env(request):
+    return Env(request.param)
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def dev_odos(odos):
+    return [tuple(dev(f) for f in o) for o in odos]
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def verdict(ff):
+    """A host verdict as it is, a device verdict word as -1 / index."""
+    if isinstance(ff, int):
+        return ff
+    import torch
+    torch.cuda.synchronize()
+    v = int(ff.item())
+    return -1 if v == NF else v
+
+
+def texts_of(odos):
+    return [[base64.b64encode(np.ascontiguousarray(f).tobytes()) for f in o] for o in odos]
+
+
+def dev_texts(texts):
+    import torch
+    return [[torch.frombuffer(bytearray(t), dtype=torch.uint8).cuda() for t in o] for o in texts]
+
+
+def data_text(words16) -> bytes:
+    """Jackson's compact MaskedInput "data" array of the given 16-byte words."""
+    return json.dumps([{"value": base64.b64encode(bytes(w)).decode()} for w in words16],
+                      separators=(",", ":")).encode()
+
+
+def jackson_text(signed_pairs) -> bytes:
+    return ("[" + ",".join('{"a":%d,"b":%d}' % ab for ab in signed_pairs) + "]").encode()
+
+
+# ---- K_RV / K_MASK / recombine / verify --------------------------------------------
+@pytest.mark.parametrize("n", FC.PARTY_COUNTS)
+def test_recombine_verify(env, n):
+    rows, odos, oy = env.rv(n)
+    FC.rv_coverage(env.pr, rows)
+    for mode in ("host", "device"):
+        arrays = odos if mode == "host" else dev_odos(odos)
+        y, ff = env.ctx.recombine_verify(arrays)
+        assert verdict(ff) == -1, mode
+        assert np.array_equal(y if mode == "host" else host(y), oy), mode
+        for at in FC.fault_positions(rows.W):
+            bad = FC.with_fault(odos, at)
+            y, ff = env.ctx.recombine_verify(bad if mode == "host" else dev_odos(bad))
+            assert verdict(ff) == at, (mode, at)
+            assert np.array_equal(y if mode == "host" else host(y), oy), (mode, at)  # written for every word
+
+
+@pytest.mark.parametrize("n", FC.PARTY_COUNTS)
+def test_mask_input(env, n):
+    pr = env.pr
+    rows, odos, _ = env.rv(n)
+    W = rows.W
+    secrets = env.secrets(W)
+    FC.assert_noncanonical(pr, secrets)
+    exp = FC.mask_words(pr, secrets, rows.ys)
+    om, off = env.F.mask_input(FC.arr(secrets), odos)
+    assert off == -1 and FC.ints(om) == exp
+    # K_MASK's secret product is the product-scanning form: one equal to 0 and one to p - 1
+    prods = {s * pr.r2 * pow(FC.M128, -1, pr.p) % pr.p for s in secrets}
+    assert 0 in prods and pr.p - 1 in prods
+    sec = FC.arr(secrets)
+    S = W - 37  # a verify-only tail of 37 mask words
+    for mode in ("host", "device"):
+        d = (lambda a: a) if mode == "host" else dev
+        h = (lambda a: a) if mode == "host" else host
+        arrays = odos if mode == "host" else dev_odos(odos)
+        out, ff = env.ctx.mask_input(arrays, d(sec))
+        assert verdict(ff) == -1 and np.array_equal(h(out), om), mode
+        out, ff = env.ctx.mask_input(arrays, d(sec[:S]))
+        assert verdict(ff) == -1 and np.array_equal(h(out), om[:S]), mode
+        for at in FC.fault_positions(W):  # the last one lies in the verify-only tail
+            bad = FC.with_fault(odos, at)
+            out, ff = env.ctx.mask_input(bad if mode == "host" else dev_odos(bad), d(sec[:S]))
+            assert verdict(ff) == at, (mode, at)
+
+
+@pytest.mark.parametrize("n", FC.PARTY_COUNTS)
+def test_recombine_then_verify_columns(env, n):
+    rows, odos, _ = env.rv(n)
+    cols = []
+    for k, col in enumerate((rows.ys, rows.rs, rows.vs, rows.ws, rows.us)):
+        exp = env.F.recombine([o[k] for o in odos])
+        assert FC.ints(exp) == list(col)
+        got = env.ctx.recombine([o[k] for o in odos])
+        assert np.array_equal(got, exp), k
+        assert np.array_equal(host(env.ctx.recombine([dev(o[k]) for o in odos])), exp), k
+        cols.append(got)
+    y, r, v, w, u = cols
+    assert env.ctx.verify(y, r, u, v, w) == -1
+    assert verdict(env.ctx.verify(*[dev(x) for x in (y, r, u, v, w)])) == -1
+    for at in FC.fault_positions(rows.W):
+        wrong = FC.arr([(x + 1) % env.pr.p if i == at else x for i, x in enumerate(rows.ws)])
+        assert env.ctx.verify(y, r, u, v, wrong) == at
+        wrong_u = FC.arr([(x + 1) % env.pr.p if i == at else x for i, x in enumerate(rows.us)])
+        assert env.ctx.verify(y, r, wrong_u, v, w) == at
+
+
+# ---- codecs ------------------------------------------------------------------------
+def test_codecs(env):
+    pr = env.pr
+    E = FC.edge_words(pr.p)
+    FC.assert_noncanonical(pr, E)
+    a = FC.arr(E)
+    assert FC.ints(env.ctx.to_gfp(a)) == [FC.to_gfp(pr, x % pr.p) for x in E]
+    assert FC.ints(env.ctx.from_gfp(a)) == [FC.from_gfp(pr, x) for x in E]
+    assert FC.ints(host(env.ctx.to_gfp(dev(a)))) == [FC.to_gfp(pr, x % pr.p) for x in E]
+    assert FC.ints(host(env.ctx.from_gfp(dev(a)))) == [FC.from_gfp(pr, x) for x in E]
+    secrets = [s for s in E for _ in E]
+    masks = [m for _ in E for m in E]
+    exp = FC.mask_words(pr, secrets, masks)
+    assert FC.ints(env.ctx.mask_words(FC.arr(secrets), FC.arr(masks))) == exp
+    assert FC.ints(host(env.ctx.mask_words(dev(FC.arr(secrets)), dev(FC.arr(masks))))) == exp
+
+
+# ---- K_CONV --------------------------------------------------------------------------
+@pytest.mark.parametrize("zero", [False, True])
+def test_convert_share(env, zero):
+    pr = env.pr
+    E = FC.edge_words(pr.p)
+    L = len(E)
+    masked = [E[i // L] for i in range(L * L)]
+    tuples = [(E[i % L], E[(i // L + 2 * i + 1) % L]) for i in range(L * L)]
+    for col in (masked, [t[0] for t in tuples], [t[1] for t in tuples]):
+        FC.assert_noncanonical(pr, col)
+    m16 = FC.arr(masked)
+    tup = FC.arr([x for t in tuples for x in t], 32)
+    text = data_text(m16)
+    for key in (0, 1, pr.p - 1, FC.UNIFORM_WORDS[0] % pr.p):
+        exp = env.F.convert_share(m16, tup, key, zero)
+        assert FC.ints(exp) == [x for t in FC.convert_share(pr, masked, tuples, key, zero) for x in t]
+        assert np.array_equal(env.ctx.convert_share(m16, tup, key, zero), exp), key
+        assert np.array_equal(host(env.ctx.convert_share(dev(m16), dev(tup), key, zero)), exp), key
+        assert np.array_equal(env.ctx.convert_share_json(text, tup, key, zero), exp), key
+        out, bad = env.ctx.convert_share_json(dev(np.frombuffer(text, np.uint8).copy()), dev(tup), key, zero)
+        assert verdict(bad) == -1 and np.array_equal(host(out), exp), key
+
+
+# ---- party kernels ---------------------------------------------------------------------
+def post_arrays(rows):
+    ys, m1s, m2s, _ = rows.own
+    W = rows.W
+    masks = FC.arr([x for i in range(W) for x in (m1s[i], 1, m2s[i], 2)], 32)
+    trip = FC.arr([x for a, b, c in rows.triples for x in (a, 3, b, 4, c, 5)], 96)
+    return masks, trip
+
+
+def test_odo_pre(env):
+    pr = env.pr
+    rows = FC.post_rows(pr.id, 2)
+    ys, m1s, m2s, own = rows.own
+    masks, trip = post_arrays(rows)
+    for col in (ys, m1s, m2s, [t[0] for t in rows.triples], [t[1] for t in rows.triples]):
+        FC.assert_noncanonical(pr, col)
+    assert any(d < 0 for pair in own for d in pair) and any(d > 0 for pair in own for d in pair)
+    assert any(d == 0 for pair in own for d in pair)
+    for stride in (16, 32):
+        share = FC.arr([x for y in ys for x in ([y] if stride == 16 else [y, FC.MASK128 - y])], stride)
+        exp = env.F.odo_pre(share, stride, masks, trip)
+        assert FC.ints(exp[0]) == list(ys) and FC.ints(exp[1]) == list(m1s) and FC.ints(exp[2]) == list(m2s)
+        assert FC.signed_of(exp[3], exp[4]) == list(own)
+        got = env.ctx.odo_pre(share, stride, masks, trip)
+        for g, e in zip(got, exp):
+            assert np.array_equal(g, e), stride
+        got = env.ctx.odo_pre(dev(share), stride, dev(masks), dev(trip))
+        for g, e in zip(got, exp):
+            assert np.array_equal(host(g), e), stride
+
+
+@pytest.mark.parametrize("n", FC.PARTY_COUNTS)
+def test_open_and_post(env, n):
+    pr = env.pr
+    rows = FC.post_rows(pr.id, n)
+    W = rows.W
+    masks, trip = post_arrays(rows)
+    own_mag, own_neg = FC.signed_arrays(signed_pairs=rows.own[3])
+    mags, negs = [own_mag], [own_neg]
+    for pm, pg in rows.partners:
+        m, g = FC.signed_arrays(mags=pm, negs=pg)
+        mags.append(m)
+        negs.append(g)
+    opened_py = FC.post_opened(pr, rows)
+    # -- coverage, on the inputs alone ---------------------------------------------------
+    if n >= 2:
+        flat = [x for pm, _ in rows.partners for pair in pm for x in pair]
+        FC.assert_noncanonical(pr, flat)
+        first = list(zip(*rows.partners[0]))
+        assert ((0, 0), (1, 1)) in first and ((pr.p, pr.p), (1, 1)) in first  # negative zero, negative p
+        assert FC.MASK128 in flat
+    assert opened_py[0] == (pr.p - 1, pr.p - 1) and rows.triples[0][:2] == (FC.MASK128, FC.MASK128)
+    # dot2_redc: 0 / 1 / 2 subtracts everywhere, hi == 2 where 3p > 2^129 (max128), on a
+    # non-player-0 row (player 0's second operand b + [E] is reduced below p)
+    cov = FC.assert_dot2_coverage(pr, FC.post_dot2_rows(pr, rows, opened_py, False))
+    assert (cov["hi2"] > 0) == (pr.id == "max128")
+    # -- reference: Python ints and the C oracle agree -------------------------------------
+    opened = env.F.recombine_diffs(mags, negs)
+    o = FC.ints(opened)
+    assert list(zip(o[0::2], o[1::2])) == opened_py
+    assert np.array_equal(env.ctx.open_diffs(mags, negs), opened)
+    assert np.array_equal(host(env.ctx.open_diffs([dev(m) for m in mags], [dev(g) for g in negs])), opened)
+    for p0 in (True, False):
+        ew, eu = env.F.odo_post(opened.reshape(2 * W, 32), trip, p0)
+        pw, pu = FC.post_expected(pr, rows, opened_py, p0)
+        assert FC.ints(ew) == pw and FC.ints(eu) == pu
+        w, u = env.ctx.odo_post(opened, trip, p0)
+        assert np.array_equal(w, ew) and np.array_equal(u, eu), p0
+        w, u = env.ctx.odo_post(dev(opened), dev(trip), p0)
+        assert np.array_equal(host(w), ew) and np.array_equal(host(u), eu), p0
+        w, u = env.ctx.open_post(mags, negs, trip, p0)
+        assert np.array_equal(w, ew) and np.array_equal(u, eu), p0
+        w, u = env.ctx.open_post([dev(m) for m in mags], [dev(g) for g in negs], dev(trip), p0)
+        assert np.array_equal(host(w), ew) and np.array_equal(host(u), eu), p0
+
+
+# ---- wire-fused (the mont_mul_ps kernels) -----------------------------------------------
+# 1, 3, 5 and, since below 2^127 the wire kernels are templated for 1..2 parties only (3 and 5 both
+# take the run-time loop there), 2 for the templated multi-party !BIG form and 4 for the BIG one
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5])
+def test_wire_fused(env, n):
+    rows, odos, oy = env.rv(n)
+    FC.rv_coverage(env.pr, rows)
+    W = rows.W
+    secrets = env.secrets(W)
+    sec = FC.arr(secrets)
+    om, _ = env.F.mask_input(sec, odos)
+    assert FC.ints(om) == FC.mask_words(env.pr, secrets, rows.ys)
+    records = [base64.b64encode(w.tobytes()) for w in om]
+    texts = texts_of(odos)
+    for mode in ("host", "device"):
+        d = (lambda a: a) if mode == "host" else dev
+        h = (lambda a: a) if mode == "host" else host
+        tx = texts if mode == "host" else dev_texts(texts)
+        y, ff, bad = env.ctx.recombine_verify_b64(tx, W)
+        assert verdict(ff) == -1 and verdict(bad) == -1 and np.array_equal(h(y), oy), mode
+        m16, rec, ff, bad = env.ctx.mask_input_b64(tx, W, d(sec), records=True, raw=True)
+        assert verdict(ff) == -1 and verdict(bad) == -1 and np.array_equal(h(m16), om), mode
+        assert [r.tobytes() for r in h(rec)] == records, mode
+        text, ff, bad = env.ctx.mask_input_json(tx, W, d(sec))
+        assert verdict(ff) == -1 and verdict(bad) == -1, mode
+        assert (text if mode == "host" else host(text).tobytes()) == data_text(om), mode
+        for at in FC.fault_positions(W):
+            bt = texts_of(FC.with_fault(odos, at))
+            bt = bt if mode == "host" else dev_texts(bt)
+            y, ff, bad = env.ctx.recombine_verify_b64(bt, W)
+            assert verdict(ff) == at and verdict(bad) == -1 and np.array_equal(h(y), oy), (mode, at)
+            _, _, ff, bad = env.ctx.mask_input_b64(bt, W, d(sec))
+            assert verdict(ff) == at and verdict(bad) == -1, (mode, at)
+            _, ff, bad = env.ctx.mask_input_json(bt, W, d(sec))
+            assert verdict(ff) == at and verdict(bad) == -1, (mode, at)
+
+
+# ---- segmented ----------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5])  # every templated form of k_rv_seg / k_mask_seg and the run-time one
+def test_packed(env, n):
+    """The same rows as a few objects of unequal length; a fault in the first
+    and in the last object; one verdict per object."""
+    import torch
+    rows, odos, oy = env.rv(n)
+    W = rows.W
+    secrets = env.secrets(W)
+    sec = FC.arr(secrets)
+    om, _ = env.F.mask_input(sec, odos)
+    offsets = np.array([0, 1, 130, W // 2 + 3, W - 2, W], np.uint64)
+    K = len(offsets) - 1
+    clean = [-1] * K
+    bad = FC.with_fault(FC.with_fault(odos, 0), W - 1)
+    faulty = [0, -1, -1, -1, 1]
+    # the reference's per-object verdicts: each object verified on its own
+    for k in range(K):
+        lo, hi = int(offsets[k]), int(offsets[k + 1])
+        _, off = env.F.recombine_verify([tuple(f[lo:hi] for f in o) for o in bad])
+        assert off == faulty[k]
+        assert FC.recombine_verify(env.pr, [tuple(FC.ints(f[lo:hi]) for f in o) for o in bad])[1] == faulty[k]
+    for arrays, want in ((odos, clean), (bad, faulty)):
+        y, ff = env.ctx.recombine_verify_packed(arrays, offsets)
+        assert ff.tolist() == want and np.array_equal(y, oy)
+        m, ff = env.ctx.mask_input_packed(arrays, offsets, sec)
+        assert ff.tolist() == want and np.array_equal(m, om)
+        y, ff = env.ctx.recombine_verify_packed(dev_odos(arrays), offsets)
+        torch.cuda.synchronize()
+        assert [(-1 if v == NF else v) for v in host(ff).tolist()] == want and np.array_equal(host(y), oy)
+        m, ff = env.ctx.mask_input_packed(dev_odos(arrays), offsets, dev(sec))
+        torch.cuda.synchronize()
+        assert [(-1 if v == NF else v) for v in host(ff).tolist()] == want and np.array_equal(host(m), om)
+
+
+# ---- party session ----------------------------------------------------------------------------
+def party_inputs(pr, j, W):
+    """Party j's share / mask / triple words on the grid, each party at its own stride."""
+    E = FC.edge_words(pr.p)
+    L = len(E)
+    ys = [E[(i * (j + 1) + 2 * j) % L] for i in range(W)]
+    m1s = [E[(i // L + (3 + j) * i + j) % L] for i in range(W)]
+    m2s = [E[((7 + 2 * j) * i + 2) % L] for i in range(W)]
+    triples = [(E[(k // L + j) % L], E[(k + 5 * j) % L], E[(k // L + 2 * k + 1 + j) % L]) for k in range(2 * W)]
+    # pair 0 carries the largest magnitudes: d = (p - 1) - 0 and e = 0 - (p - 1)  (fromGfp(p - R) = p - 1)
+    ys[0], m1s[0] = pr.p - pr.r, 0
+    triples[0] = (0, pr.p - pr.r, triples[0][2])
+    return ys, m1s, m2s, triples
+
+
+@pytest.mark.parametrize("n", [2, 3])
+def test_party_session(env, n):
+    pr = env.pr
+    L = len(FC.edge_words(pr.p))
+    W = L * L // 2
+    ins = [party_inputs(pr, j, W) for j in range(n)]
+    own = [FC.odo_pre(pr, *ins[j]) for j in range(n)]
+    mags = [x for o in own for pair in o for x in map(abs, pair)]
+    assert max(mags) == pr.p - 1  # the longest decimal magnitude the text can carry
+    if pr.id == "max128":
+        assert len(str(max(mags))) == 39
+    arrays = []
+    for j in range(n):
+        ys, m1s, m2s, triples = ins[j]
+        share = FC.arr([x for y in ys for x in (y, FC.MASK128 - y)], 32)
+        masks = FC.arr([x for i in range(W) for x in (m1s[i], 1, m2s[i], 2)], 32)
+        trip = FC.arr([x for a, b, c in triples for x in (a, 3, b, 4, c, 5)], 96)
+        arrays.append((share, masks, trip))
+    pre = [env.F.odo_pre(a[0], 32, a[1], a[2]) for a in arrays]
+    for j in range(n):
+        assert FC.signed_of(pre[j][3], pre[j][4]) == own[j]
+    sessions, texts = [], []
+    for j in range(n):
+        s = env.ctx.party_begin(arrays[j][0], 32, arrays[j][1], arrays[j][2], n)
+        assert FC.ints(s.y) == ins[j][0] and FC.ints(s.r) == ins[j][1] and FC.ints(s.v) == ins[j][2]
+        t = s.text()
+        assert t == jackson_text(own[j])
+        sessions.append(s)
+        texts.append(t)
+    for j, s in enumerate(sessions):
+        others = [k for k in range(n) if k != j]
+        for slot, k in enumerate(others, start=1):
+            s.partner(slot, texts[k])
+        flat = [[x for pair in own[k] for x in pair] for k in [j] + others]
+        o = FC.open_values(pr, flat)
+        opened = list(zip(o[0::2], o[1::2]))
+        z = [FC.post_word(pr, D, E, t, j == 0) for (D, E), t in zip(opened, ins[j][3])]
+        ow, ou = env.F.odo_post(env.F.recombine_diffs([pre[k][3] for k in [j] + others],
+                                                      [pre[k][4] for k in [j] + others]), arrays[j][2], j == 0)
+        assert FC.ints(ow) == z[0::2] and FC.ints(ou) == z[1::2]
+        if j == n - 1:
+            got = s.finish_b64(j == 0)
+            assert got == [base64.b64encode(x.tobytes()) for x in (pre[j][0], pre[j][1], pre[j][2], ow, ou)]
+        else:
+            w, u = s.finish(j == 0)
+            assert np.array_equal(w, ow) and np.array_equal(u, ou)
+        s.close()
+
+
+# ---- device synth ---------------------------------------------------------------------------------
+def test_device_synth(env):
+    import torch
+    pr = env.pr
+    W = 2500
+    as_ints = lambda od: [tuple(FC.ints(host(f)) for f in o) for o in od]  # noqa: E731
+    for n, permille in ((1, 0), (3, 0), (3, 300), (16, 300)):
+        odos, _, plain = env.ctx.synth_odos(seed=11 + n, n=n, words=W, noncanon_permille=permille, with_plain=True)
+        torch.cuda.synchronize()
+        hodos = [tuple(host(f) for f in o) for o in odos]
+        oy, off = env.F.recombine_verify(hodos)
+        assert off == -1 and np.array_equal(oy, host(plain)), (n, permille)
+        assert FC.recombine_verify(pr, as_ints(odos)) == (FC.ints(oy), -1)
+    for n, at in ((1, 0), (2, W - 1), (3, W // 2)):
+        odos, _, _ = env.ctx.synth_odos(seed=7, n=n, words=W, fault_index=at)
+        torch.cuda.synchronize()
+        _, off = env.F.recombine_verify([tuple(host(f) for f in o) for o in odos])
+        assert off == at, (n, at)
+        assert FC.recombine_verify(pr, as_ints(odos))[1] == at
+    words = host(env.ctx.synth_words(seed=9, count=W))
+    assert all(x < pr.p for x in FC.ints(words))
+    # the same counter-based generator as the oracle's: the 128-bit hash of (seed, i) mod p
+    assert np.array_equal(words, env.F.synth_words(seed=9, count=W, mont=False))

@@ -81,11 +81,10 @@ def test_odo_kernels_edges(ctx, F, W, n, p0, data):
     exp = F.odo_pre(share, 16, masks, trip)
     for g, e in zip(got, exp):
         assert np.array_equal(g, e)
-    # partners: arbitrary signed diffs with magnitudes < p
+    # partners: arbitrary signed diffs, raw magnitudes (>= p included: the kernels and the oracle reduce them)
     mags, negs = [got[3]], [got[4]]
     for _ in range(n - 1):
-        mags.append(arr([v % P for v in data.draw(st.lists(raw_word, min_size=4 * W, max_size=4 * W))])
-                    .reshape(2 * W, 2, 16))
+        mags.append(arr(data.draw(st.lists(raw_word, min_size=4 * W, max_size=4 * W))).reshape(2 * W, 2, 16))
         negs.append(np.array(data.draw(st.lists(st.integers(0, 1), min_size=4 * W, max_size=4 * W)),
                              np.uint8).reshape(2 * W, 2))
     opened = ctx.open_diffs(mags, negs)
