@@ -472,7 +472,10 @@ int amph_recombine_verify_b64(amph_ctx* ctx, const amph_odo_b64* odos, int n_par
  * n_secrets > words: the texts are decoded and every mask verified first (a
  * bad character or a MAC failure is reported as such, as the reference
  * decodes and verifies before it indexes, DefaultAmphoraClient.java:153-160),
- * and only then AMPH_E_LEN; device mode waits for the verdicts on that path. */
+ * and only then AMPH_E_LEN; device mode waits for the verdicts on that path,
+ * so in both modes a bad character returns AMPH_E_PARAM with *bad_char set
+ * and a MAC failure AMPH_E_VERIFY with *first_fail set, and neither output
+ * array is written. */
 int amph_mask_input_b64(amph_ctx* ctx, const amph_odo_b64* mask_odos, int n_parties, size_t words,
                         const uint8_t* secrets, size_t n_secrets, uint8_t* out_masked16,
                         char* out_records24, int64_t* first_fail, int64_t* bad_char, uint32_t flags,
@@ -536,7 +539,8 @@ int amph_mask_input_json(amph_ctx* ctx, const amph_odo_b64* mask_odos, int n_par
  *   default output; *out_len = its length.  Device mode: out_cap must be
  *   >= amph_exchange_max_chars(npairs) and out_len is a device word, written
  *   asynchronously.  Host mode: AMPH_E_LEN with *out_len = the needed length
- *   if out_cap is too small.
+ *   if out_cap is too small.  The bytes of out from *out_len up to out_cap
+ *   are unspecified; nothing at or past out + out_cap is written.
  * decode: text = the array (whitespace between tokens allowed; member order
  *   "a","b" or "b","a").  A malformed token returns AMPH_E_PARAM with
  *   *bad_index = its byte offset; a count other than npairs pairs returns
