@@ -130,6 +130,16 @@ def _load():
     L.amph_party_partner_dev.argtypes = [vp, i32, vp, sz, vp, vp]
     L.amph_party_finish_b64_dev.argtypes = [vp, i32, C.POINTER(vp), vp]
     L.amph_party_reset_partner.argtypes = [vp, i32]
+    # include/amphora_wire_batch.h
+    pp = C.POINTER(vp)
+    L.amph_wire_slot_chars.restype = sz
+    L.amph_wire_slot_chars.argtypes = [sz]
+    L.amph_wire_batch_copies.restype = u64
+    L.amph_wire_batch_copies.argtypes = [vp]
+    L.amph_recombine_verify_b64_packed.argtypes = [vp, vp, i32, vp, vp, sz, vp, vp, vp, u32, vp]
+    L.amph_mask_input_b64_packed.argtypes = [vp, vp, i32, vp, vp, sz, vp, vp, vp, vp, vp, u32, vp]
+    L.amph_recombine_verify_b64_batch.argtypes = [vp, vp, i32, sz, C.POINTER(sz), pp, i64p, i64p, u32]
+    L.amph_mask_input_b64_batch.argtypes = [vp, vp, i32, sz, C.POINTER(sz), pp, pp, pp, i64p, i64p, u32]
     return L
 
 
@@ -179,6 +189,29 @@ EXPORTED = ["amph_ctx_create", "amph_ctx_create_multi", "amph_ctx_device_count",
             "amph_party_text", "amph_party_partner", "amph_party_finish", "amph_party_finish_b64",
             "amph_party_free", "amph_party_begin_dev", "amph_party_text_dev", "amph_party_partner_dev",
             "amph_party_finish_b64_dev", "amph_party_reset_partner"]
+# what include/amphora_wire_batch.h declares (the extension header keeps its own list)
+EXPORTED_WIRE_BATCH = ["amph_wire_slot_chars", "amph_wire_batch_copies", "amph_recombine_verify_b64_packed",
+                       "amph_mask_input_b64_packed", "amph_recombine_verify_b64_batch",
+                       "amph_mask_input_b64_batch"]
+ODO_FIELD_NAMES = ("secretShares", "rShares", "vShares", "wShares", "uShares")
+
+
+def wire_text_chars(words: int) -> int:
+    """Characters of the base64 text of `words` 16-byte words, padding included."""
+    return 4 * ((16 * words + 2) // 3)
+
+
+def wire_slot_chars(words: int) -> int:
+    """amph_wire_slot_chars: the text rounded up to whole 16-character units."""
+    return int(lib.amph_wire_slot_chars(words))
+
+
+def wire_bad_char_message(bad: int, words: int) -> str:
+    """The single wire-text call's message for a bad_char verdict of an object
+    of `words` words ((5 party + field) * nchars + offset)."""
+    nc = wire_text_chars(words)
+    return "Illegal base64 character at index %d of party %d's %s" % (
+        bad % nc, bad // nc // 5, ODO_FIELD_NAMES[bad // nc % 5])
 
 
 class TimingEvent:
@@ -726,6 +759,134 @@ class Context:
             raise ValueError(lib.amph_last_error().decode())
         self._check(st, allow_verify=True)
         return (out if _is_dev(sv) else out.tobytes()), self._ff_value(ff), self._ff_value(bad)
+
+    # -- many secrets straight from their wire texts (include/amphora_wire_batch.h) --
+    def wire_batch_copies(self) -> int:
+        """amph_wire_batch_copies: host-device copies of the host-mode calls below."""
+        return int(lib.amph_wire_batch_copies(self._h))
+
+    def _wire_packed(self, masked, texts, word_offsets, text_offsets, secrets16, records, raw, first_fail,
+                     bad_char, accumulate, status):
+        arr, keep = self._text_structs(texts)
+        s = words_view(secrets16) if masked else None
+        flags, stream = self._mode(s, *keep)
+        like = keep[0]
+        wo = np.ascontiguousarray(word_offsets, dtype=np.uint64) if not _is_dev(word_offsets) else word_offsets
+        to = np.ascontiguousarray(text_offsets, dtype=np.uint64) if not _is_dev(text_offsets) else text_offsets
+        K = max(0, (wo.numel() if _is_dev(wo) else wo.size) - 1)
+        if (to.numel() if _is_dev(to) else to.size) != K:
+            raise ValueError("one text offset per object, one more word offset")
+        T = int(wo[-1]) if K else 0
+        if flags & AMPH_F_DEVICE:
+            import torch
+            wo, to = [x if _is_dev(x) else torch.as_tensor(x.view(np.int64)).to(like.device) for x in (wo, to)]
+            verdicts = []
+            for v in (first_fail, bad_char):
+                if v is None:
+                    v = torch.empty(K, dtype=torch.int64, device=like.device)
+                    accumulate = False
+                elif v.numel() != K or v.dtype != torch.int64 or not v.is_cuda:
+                    raise ValueError("verdict arrays must be int64 device tensors with one entry per object")
+                verdicts.append(v)
+            first_fail, bad_char = verdicts
+            if accumulate:
+                flags |= AMPH_F_ACCUMULATE
+        else:
+            first_fail = np.full(K, -1, dtype=np.int64)
+            bad_char = np.full(K, -1, dtype=np.int64)
+        if masked:
+            _need(s.shape[0] == T, "the packed form takes one secret per input mask word")
+            o16 = self._empty(like, (T, 16)) if raw else None
+            o24 = self._empty(like, (T, 24)) if records else None
+            st = lib.amph_mask_input_b64_packed(self._h, arr, len(texts), _ptr(wo), _ptr(to), K, _ptr(s),
+                                                _ptr(o16), _ptr(o24), _ptr(first_fail), _ptr(bad_char), flags,
+                                                stream)
+            res = (o16, o24, first_fail, bad_char)
+        else:
+            out = self._empty(like, (T, 16))
+            st = lib.amph_recombine_verify_b64_packed(self._h, arr, len(texts), _ptr(wo), _ptr(to), K, _ptr(out),
+                                                      _ptr(first_fail), _ptr(bad_char), flags, stream)
+            res = (out, first_fail, bad_char)
+        return self._wire_batch_result(st, res, bad_char, status)
+
+    def _wire_batch_result(self, st, res, bad_char, status):
+        """Per-object verdicts are the result: AMPH_E_VERIFY, and AMPH_E_PARAM
+        with a bad character reported, return them (status=True appends
+        (status, amph_last_error)); anything else raises."""
+        msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
+        if not (st == AMPH_E_PARAM and not _is_dev(bad_char) and (np.asarray(bad_char) >= 0).any()):
+            self._check(st, allow_verify=True)
+        return res + ((st, msg),) if status else res
+
+    def recombine_verify_b64_packed(self, texts, word_offsets, text_offsets, first_fail=None, bad_char=None,
+                                    accumulate=False, status=False):
+        """K secrets from their base64 texts in one launch.  texts: per party
+        the five field buffers, each holding every object's text at
+        text_offsets[o] (multiples of 16, the same in all buffers);
+        word_offsets: K + 1 word offsets of the packed outputs.  Returns
+        (secrets (T, 16), first_fail[K], bad_char[K]): host -- -1 or the
+        object's own index; device -- int64 tensors of AMPH_NO_FAILURE /
+        index (pass them back with accumulate=True to min-combine)."""
+        return self._wire_packed(False, texts, word_offsets, text_offsets, None, False, False, first_fail,
+                                 bad_char, accumulate, status)
+
+    def mask_input_b64_packed(self, texts, word_offsets, text_offsets, secrets16, records=True, raw=False,
+                              first_fail=None, bad_char=None, accumulate=False, status=False):
+        """recombine_verify_b64_packed over Input Mask ODO texts fused with
+        maskInput, one secret per mask word: (masked (T, 16) or None, records
+        (T, 24) or None, first_fail[K], bad_char[K])."""
+        return self._wire_packed(True, texts, word_offsets, text_offsets, secrets16, records, raw, first_fail,
+                                 bad_char, accumulate, status)
+
+    def _wire_batch(self, masked, objects, words, secrets, records, raw, status):
+        K = len(objects)
+        n = len(objects[0]) if K else 1
+        arr = (_AmphOdoB64 * max(1, K * n))()
+        keep = []
+        for o, obj in enumerate(objects):
+            if len(obj) != n:
+                raise ValueError("every object needs the same number of parties")
+            a, ks = self._text_structs(obj)
+            if any(_is_dev(f) for f in ks):
+                raise ValueError("the batch calls take host buffers")
+            keep.append(ks)
+            for j in range(n):
+                arr[o * n + j] = a[j]
+        wd = (C.c_size_t * max(1, K))(*[int(w) for w in words])
+        ff = np.full(K, -1, dtype=np.int64)
+        bad = np.full(K, -1, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        ptrs = lambda xs: (C.c_void_p * max(1, K))(*[x.ctypes.data for x in xs]) if xs is not None else None
+        if masked:
+            if len(secrets) != K:
+                raise ValueError("one secrets array per object")
+            sv = [words_view(x) for x in secrets]
+            for o in range(K):
+                _need(sv[o].shape[0] == int(words[o]), "object %d: one secret per input mask word" % o)
+            o16 = [np.empty((int(w), 16), np.uint8) for w in words] if raw else None
+            o24 = [np.empty((int(w), 24), np.uint8) for w in words] if records else None
+            st = lib.amph_mask_input_b64_batch(self._h, arr, n, K, wd, ptrs(sv), ptrs(o16), ptrs(o24),
+                                               ff.ctypes.data_as(i64p), bad.ctypes.data_as(i64p), 0)
+            res = (o16, o24, ff, bad)
+        else:
+            outs = [np.empty((int(w), 16), np.uint8) for w in words]
+            st = lib.amph_recombine_verify_b64_batch(self._h, arr, n, K, wd, ptrs(outs), ff.ctypes.data_as(i64p),
+                                                     bad.ctypes.data_as(i64p), 0)
+            res = (outs, ff, bad)
+        return self._wire_batch_result(st, res, bad, status)
+
+    def recombine_verify_b64_batch(self, objects, words, status=False):
+        """objects: list over secrets of recombine_verify_b64's `texts` (host
+        strings / bytes), words[o] each object's word count.  One launch;
+        returns (list of (W_o, 16) secrets, first_fail[K], bad_char[K]) -- per
+        object what recombine_verify_b64 gives."""
+        return self._wire_batch(False, objects, words, None, False, False, status)
+
+    def mask_input_b64_batch(self, objects, words, secrets, records=True, raw=False, status=False):
+        """mask_input_b64 for K secrets at once, secrets[o] of exactly words[o]
+        words: (list of masked (W_o, 16) or None, list of records (W_o, 24) or
+        None, first_fail[K], bad_char[K])."""
+        return self._wire_batch(True, objects, words, secrets, records, raw, status)
 
     # -- wire codec (base64 as Jackson writes byte[]) ---------------------------
     def base64_encode(self, data) -> bytes:

@@ -339,6 +339,91 @@ def create_masked_input_json(util: SecretShareUtil, secret: Secret, odo_bodies: 
     return wire.records_to_masked_input_json(secret.secret_id, rec, secret.tags)
 
 
+# ---- many secrets per launch, from their JSON bodies --------------------------------
+# verify_vss_json / create_masked_input_json for K secrets over ONE launch
+# (amph_recombine_verify_b64_batch / amph_mask_input_b64_batch): one entry per
+# secret, the value or the exception the single function raises for it.
+
+def _body_texts(bodies):
+    """(texts, W) of one secret's bodies, or the exception _texts_and_words
+    raises (that secret then goes through the single function, which raises
+    it again as its own)."""
+    try:
+        return _texts_and_words(bodies)
+    except Exception:  # malformed JSON, unequal field lengths, not whole words
+        return None, None
+
+
+def _wire_batch_outcomes(util, parsed, regular, run, finish, single):
+    out = [None] * len(parsed)
+    idx = [o for o, r in enumerate(regular) if r]
+    if idx:
+        values, ff, bad = run(idx)
+        for k, o in enumerate(idx):
+            texts, W = parsed[o]
+            if bad[k] >= 0:
+                out[o] = AmphoraClientException(_lib.wire_bad_char_message(int(bad[k]), W))
+            elif ff[k] >= 0:
+                out[o] = _outcome(_raise_for_texts, util, texts, int(ff[k]))
+            else:
+                out[o] = _outcome(finish, o, values[k])
+    for o, r in enumerate(regular):
+        if not r:
+            out[o] = _outcome(single, o)
+    return out
+
+
+def verify_vss_json_batch(util: SecretShareUtil, list_of_bodies_lists, secret_ids=None):
+    """verify_vss_json for K secrets in one launch.  Returns one entry per
+    secret: (secretId, tags, canonical secrets), or the exception
+    verify_vss_json raises for that secret -- IntegrityVerificationException
+    with the reference's message for a MAC failure, AmphoraClientException with
+    the single call's text for an illegal base64 character.  A secret with
+    another party count than the first, or with malformed bodies, goes
+    through verify_vss_json itself."""
+    from . import wire
+    parsed = [_body_texts(b) for b in list_of_bodies_lists]
+    n = next((len(t) for t, _ in parsed if t), 0)
+    regular = [t is not None and len(t) == n for t, _ in parsed]
+    sid_of = lambda o: None if secret_ids is None else secret_ids[o]  # noqa: E731
+
+    def finish(o, y):
+        b0 = list_of_bodies_lists[o][0]
+        sid, tags = wire.vss_metadata(b0, wire.odo_field_texts(b0)[1])
+        return (sid if sid_of(o) is None else sid_of(o)), tags, unpack(y)
+
+    return _wire_batch_outcomes(
+        util, parsed, regular,
+        lambda idx: util.context.recombine_verify_b64_batch([parsed[o][0] for o in idx], [parsed[o][1] for o in idx]),
+        finish,
+        lambda o: verify_vss_json(util, list_of_bodies_lists[o], sid_of(o)))
+
+
+def create_masked_inputs_from_bodies(util: SecretShareUtil, secrets: Sequence[Secret], list_of_odo_bodies_lists):
+    """create_masked_input_json for K secrets in one launch: one entry per
+    secret, the MaskedInput JSON body or the exception create_masked_input_json
+    raises for that secret.  A secret whose word count differs from its mask
+    count goes through the single function (which verifies the masks before
+    it reports the length), as do other party counts and malformed bodies."""
+    from . import wire
+    if len(secrets) != len(list_of_odo_bodies_lists):
+        raise ValueError("one list of Input Mask ODO bodies per secret")
+    parsed = [_body_texts(b) for b in list_of_odo_bodies_lists]
+    n = next((len(t) for t, _ in parsed if t), 0)
+    regular = [t is not None and len(t) == n and secrets[o].size() == W for o, (t, W) in enumerate(parsed)]
+
+    def run(idx):
+        _, rec, ff, bad = util.context.mask_input_b64_batch(
+            [parsed[o][0] for o in idx], [parsed[o][1] for o in idx],
+            [pack(secrets[o].data, util.prime) for o in idx], records=True)
+        return rec, ff, bad
+
+    return _wire_batch_outcomes(
+        util, parsed, regular, run,
+        lambda o, rec: wire.records_to_masked_input_json(secrets[o].secret_id, rec, secrets[o].tags),
+        lambda o: create_masked_input_json(util, secrets[o], list_of_odo_bodies_lists[o]))
+
+
 def create_masked_input_body(util: SecretShareUtil, secret: Secret, odo_bodies: Sequence[str]) -> str:
     """create_masked_input_json with the "data" array text written by the
     kernel itself (amph_mask_input_json): the records leave the GPU already

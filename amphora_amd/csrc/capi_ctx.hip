@@ -233,6 +233,7 @@ void amph_ctx_destroy(amph_ctx* c) {
     c->ff.release();
     c->tail.release();
     c->wire.release();
+    c->wire_img.release();
     c->xstage.release();
   }
   if (c->small.p || c->small_ff.p) {

@@ -1,7 +1,8 @@
 // Internals shared by the units of the C ABI (capi_*.hip): the context, the
 // error and device helpers, the word-array pipeline's types and the buffers
 // of one-shot host calls.  Everything here lives in one namespace of hidden
-// visibility: the library exports only what include/amphora.h declares.
+// visibility: the library exports only what include/amphora.h and its
+// extension header include/amphora_wire_batch.h declare.
 //
 // Host-pointer calls stream the word arrays through the device in batches
 // (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
@@ -28,6 +29,7 @@
 #include <thread>
 
 #include "../../include/amphora.h"
+#include "../../include/amphora_wire_batch.h"
 #include "host_stream.hpp"
 #include "kernels.hpp"
 
@@ -133,6 +135,11 @@ struct amph_ctx {
   DevBuf ff;  // per-batch first-fail words (host path)
   DevBuf tail;  // small scratch for the partial last unit of codec calls
   DevBuf wire;  // host-mode staging of the wire-text calls (texts, secrets, outputs, verdicts)
+  // the many-objects wire-text calls (amphora_wire_batch.h): the page-locked
+  // image their staged host mode gathers into and scatters from, and the
+  // hipMemcpy calls that moved it (amph_wire_batch_copies)
+  amph::PinnedBuf wire_img;
+  std::atomic<uint64_t> wire_copies{0};
   DevBuf xstage;  // host-mode staging of the exchange codec calls
   DevBuf xdev;    // device-mode scan scratch of the exchange codec calls
   hipEvent_t xdev_done = nullptr;  // the last device-mode exchange call's kernels

@@ -2,6 +2,7 @@
 // base64, the Beaver open exchange codec, K_RV / K_MASK from the wire texts
 // and K_CONV from the MaskedInput "data" array text.
 #include "capi_internal.hpp"
+#include "wiretiles.hpp"
 
 // ---- base64 wire codec ---------------------------------------------------------
 namespace {
@@ -564,6 +565,300 @@ int amph_convert_share_json(amph_ctx* c, const char* text, size_t len, size_t wo
     return fail(AMPH_E_PARAM, "Malformed MaskedInput data text at offset " + std::to_string(bad) + " (" + where + ")");
   }
   return h.fetch({{out, dout, 32 * words}});
+}
+
+}  // extern "C"
+
+// ---- K_RV / K_MASK from the wire, many objects per call -------------------------
+// include/amphora_wire_batch.h: the slotted text layout (wire.hip,
+// wiretiles.hpp).  Host mode moves ONE page-locked image to the device and one
+// back, whatever the object count: [word table | text table | 5 n field
+// buffers | secrets] in, [16-byte words | records | 2 K verdict words] out.
+// A call that fits the small-call arena builds the image there and the
+// kernel reads and writes it in place; its verdict arrays stay in device
+// memory (atomics) and come to the arena by launch_take_array before the
+// call's one synchronisation, as run_packed_small.
+namespace {
+int wire_batch_parties(const amph_odo_b64* odos, int n) {
+  if (!odos || n < 1 || n > AMPH_MAX_PARTIES)
+    return fail(AMPH_E_PARAM, "n_parties must be in [1, 16] with a non-null ODO array");
+  return AMPH_OK;
+}
+
+// the host tables of a packed call against the buffers' length
+int check_wire_tables(const uint64_t* woff, const uint64_t* toff, size_t K, size_t nchars) {
+  if (woff[0] != 0) return fail(AMPH_E_PARAM, "word_offsets[0] must be 0");
+  for (size_t o = 0; o < K; ++o)
+    if (woff[o + 1] < woff[o])
+      return fail(AMPH_E_PARAM, "word_offsets must not decrease (entry " + std::to_string(o + 1) + ")");
+  for (size_t o = 0; o < K; ++o) {
+    const uint64_t end = toff[o] + amph::wire_text_chars(woff[o + 1] - woff[o]);
+    if (toff[o] % 16)
+      return fail(AMPH_E_PARAM, "text_offsets[" + std::to_string(o) + "] = " + std::to_string(toff[o]) +
+                                    " must be a multiple of 16");
+    if (end < toff[o] || end > (o + 1 < K ? toff[o + 1] : (uint64_t)nchars))
+      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": its text [" + std::to_string(toff[o]) + ", " +
+                                    std::to_string(end) + ") runs past " +
+                                    (o + 1 < K ? "the next slot at " + std::to_string(toff[o + 1])
+                                               : "the buffers' " + std::to_string(nchars) + " characters"));
+  }
+  return AMPH_OK;
+}
+
+// The verdict words (first-fail array, then bad-character array) as the
+// caller's entries and the call's status.
+int wire_batch_status(const unsigned long long* v, size_t K, const uint64_t* woff, int64_t* first_fail,
+                      int64_t* bad_char) {
+  size_t nbad = 0, nfail = 0, fb = 0, ff = 0;
+  for (size_t o = 0; o < K; ++o) {
+    const bool bad = v[K + o] != amph::kNoFail, failed = !bad && v[o] != amph::kNoFail;
+    if (bad && !nbad++) fb = o;
+    if (failed && !nfail++) ff = o;
+    bad_char[o] = bad ? (int64_t)v[K + o] : -1;
+    first_fail[o] = failed ? (int64_t)v[o] : -1;
+  }
+  if (nbad) {
+    const size_t nc = amph::wire_text_chars(woff[fb + 1] - woff[fb]), f = (size_t)v[K + fb] / nc;
+    return fail(AMPH_E_PARAM, "object " + std::to_string(fb) + ": Illegal base64 character at index " +
+                                  std::to_string((size_t)v[K + fb] % nc) + " of party " + std::to_string(f / 5) +
+                                  "'s " + kOdoFieldNames[f % 5] + " (" + std::to_string(nbad) + " of " +
+                                  std::to_string(K) + " objects hold an illegal character)");
+  }
+  if (nfail)
+    return fail(AMPH_E_VERIFY, "Verification of secret has failed: object " + std::to_string(ff) + " at word " +
+                                   std::to_string(v[ff]) + " (" + std::to_string(nfail) + " of " +
+                                   std::to_string(K) + " objects failed)");
+  return AMPH_OK;
+}
+
+// How a host call's pieces enter and leave the image: text(j, k, o) = party
+// j's field k of object o (nchars_o characters), secrets(o) / out16(o) /
+// out24(o) = object o's words (null: not wanted).
+struct WirePieces {
+  std::function<const char*(int, int, size_t)> text;
+  std::function<const uint8_t*(size_t)> secrets;
+  std::function<uint8_t*(size_t)> out16;
+  std::function<char*(size_t)> out24;
+};
+
+// Host mode of all four calls, tables validated: woff[K + 1], toff[K] (a
+// field buffer of the image holds `chars` characters).
+int wire_batch_host(amph_ctx* c, int n, size_t K, const uint64_t* woff, const uint64_t* toff, size_t chars,
+                    bool masked, bool want16, bool want24, const WirePieces& io, int64_t* first_fail,
+                    int64_t* bad_char) {
+  const size_t T = woff[K];
+  for (size_t o = 0; o < K; ++o) first_fail[o] = bad_char[o] = -1;
+  if (T == 0) return AMPH_OK;
+  if (!c->sub.empty()) c = c->sub[0];
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(use_device(c->device));
+  hipStream_t s;
+  if (int st = host_stream(c, 0, &s)) return st;
+  const size_t fchars = align256(chars ? chars : 16);
+  const size_t tab_w = 0, tab_t = tab_w + align256(8 * (K + 1)), txt = tab_t + align256(8 * K);
+  const size_t sec = txt + 5 * (size_t)n * fchars, in_bytes = sec + (masked ? align256(16 * T) : 0);
+  const size_t o16 = in_bytes, o24 = o16 + (want16 ? align256(16 * T) : 0);
+  const size_t verd = o24 + (want24 ? align256(24 * T) : 0), total = verd + align256(16 * K);
+  const bool small = small_call(c, total);
+  uint8_t *himg, *dimg;
+  unsigned long long* dverd;
+  if (small) {
+    if (c->small.ensure(total + 256) != hipSuccess) return fail(AMPH_E_NOMEM, "small-call arena");
+    if (dev_ensure(c, c->seg, 16 * K) != hipSuccess) return fail(AMPH_E_NOMEM, "verdict arrays");
+    himg = dimg = (uint8_t*)c->small.p;
+    dverd = (unsigned long long*)c->seg.p;
+  } else {
+    if (c->wire_img.ensure(total) != hipSuccess) return fail(AMPH_E_NOMEM, "wire batch image");
+    if (dev_ensure(c, c->wire, total) != hipSuccess) return fail(AMPH_E_NOMEM, "wire staging");
+    himg = (uint8_t*)c->wire_img.p;
+    dimg = (uint8_t*)c->wire.p;
+    dverd = (unsigned long long*)(dimg + verd);
+  }
+  std::memcpy(himg + tab_w, woff, 8 * (K + 1));
+  std::memcpy(himg + tab_t, toff, 8 * K);
+  amph::TextSet tx{};
+  for (int j = 0; j < n; ++j)
+    for (int k = 0; k < 5; ++k) {
+      const size_t at = txt + (size_t)(5 * j + k) * fchars;
+      for (size_t o = 0; o < K; ++o)
+        if (const size_t nc = amph::wire_text_chars(woff[o + 1] - woff[o]))
+          std::memcpy(himg + at + toff[o], io.text(j, k, o), nc);
+      tx.t[k][j] = (const char*)(dimg + at);
+    }
+  for (size_t o = 0; masked && o < K; ++o)
+    if (woff[o + 1] > woff[o]) std::memcpy(himg + sec + 16 * woff[o], io.secrets(o), 16 * (woff[o + 1] - woff[o]));
+  if (!small) {  // page-locked image, idle stream: one blocking copy (kPageableRule)
+    HIP_TRY(hipMemcpy(dimg, himg, in_bytes, hipMemcpyHostToDevice));
+    c->wire_copies.fetch_add(1, std::memory_order_relaxed);
+  }
+  HIP_TRY(hipMemsetAsync(dverd, 0x7F, 16 * K, s));
+  const uint64_t *dw = (const uint64_t*)(dimg + tab_w), *dt = (const uint64_t*)(dimg + tab_t);
+  const size_t grid = amph::wire_tile_grid(T, K);
+  hipError_t e = masked ? amph::launch_mask_b64_seg(tx, n, dw, dt, K, grid, (const uint4*)(dimg + sec),
+                                                    want16 ? (uint4*)(dimg + o16) : nullptr,
+                                                    want24 ? (char*)(dimg + o24) : nullptr, dverd, dverd + K, c->f,
+                                                    cfg(c, s, T))
+                        : amph::launch_rv_b64_seg(tx, n, dw, dt, K, grid, (uint4*)(dimg + o16), dverd, dverd + K,
+                                                  c->f, cfg(c, s, T));
+  if (e == hipSuccess && small) e = amph::launch_take_array(dverd, (unsigned long long*)(himg + verd), 2 * K, s);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);
+    return hip_fail(e, masked ? "k_mask_b64_seg" : "k_rv_b64_seg");
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (!small) {
+    HIP_TRY(hipMemcpy(himg + in_bytes, dimg + in_bytes, total - in_bytes, hipMemcpyDeviceToHost));
+    c->wire_copies.fetch_add(1, std::memory_order_relaxed);
+  }
+  for (size_t o = 0; o < K; ++o) {
+    const size_t w0 = woff[o], w = woff[o + 1] - w0;
+    if (!w) continue;
+    if (want16) std::memcpy(io.out16(o), himg + o16 + 16 * w0, 16 * w);
+    if (want24) std::memcpy(io.out24(o), himg + o24 + 24 * w0, 24 * w);
+  }
+  return wire_batch_status((const unsigned long long*)(himg + verd), K, woff, first_fail, bad_char);
+}
+
+// Both packed calls: `masked` = false runs K_RV (out16 = the secrets out).
+int wire_packed_call(amph_ctx* c, const amph_odo_b64* odos, int n, const uint64_t* woff, const uint64_t* toff,
+                     size_t K, bool masked, const uint8_t* secrets, uint8_t* out16, char* out24,
+                     int64_t* first_fail, int64_t* bad_char, uint32_t flags, void* stream) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  AMPH_NO_HOST_IO(flags);
+  if (K == 0) return AMPH_OK;
+  if (int st = wire_batch_parties(odos, n)) return st;
+  if (!woff || !toff || !first_fail || !bad_char)
+    return fail(AMPH_E_PARAM, "null offsets table or verdict array");
+  for (int j = 1; j < n; ++j)
+    if (odos[j].nchars != odos[0].nchars)
+      return fail(AMPH_E_LEN, "party " + std::to_string(j) + ": field buffers of " + std::to_string(odos[j].nchars) +
+                                  " characters, party 0's hold " + std::to_string(odos[0].nchars));
+  const size_t nchars = odos[0].nchars;
+  if (flags & AMPH_F_DEVICE) {
+    amph::TextSet tx{};
+    for (int j = 0; j < n; ++j)
+      for (int k = 0; k < 5; ++k) {
+        tx.t[k][j] = b64_field(odos[j], k);
+        if (nchars && !tx.t[k][j]) return fail(AMPH_E_PARAM, "null ODO field text");
+        if (int st = check_dev_words({tx.t[k][j]})) return st;
+      }
+    if (int st = check_dev_words({secrets, out16, out24})) return st;
+    if (((uintptr_t)woff | (uintptr_t)toff | (uintptr_t)first_fail | (uintptr_t)bad_char) & 7)
+      return fail(AMPH_E_PARAM, "device offset tables and verdict arrays must be 8-byte aligned");
+    if (nchars && ((!masked && !out16) || (masked && !secrets))) return fail(AMPH_E_PARAM, "null secrets/output");
+    if (!c->sub.empty()) c = c->sub[0];
+    HIP_TRY(use_device(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!(flags & AMPH_F_ACCUMULATE)) {
+      HIP_TRY(hipMemsetAsync(first_fail, 0x7F, 8 * K, s));
+      HIP_TRY(hipMemsetAsync(bad_char, 0x7F, 8 * K, s));
+    }
+    // the word table is the device's: every text of W words takes at least
+    // 64 W / 3 characters of the buffers, so T <= 3 nchars / 64 bounds the
+    // grid (the surplus workgroups find no tile and exit)
+    const size_t tbound = 3 * (nchars / 64) + 3, grid = amph::wire_tile_grid(tbound, K);
+    if (nchars == 0) return AMPH_OK;
+    hipError_t e = masked ? amph::launch_mask_b64_seg(tx, n, woff, toff, K, grid, (const uint4*)secrets,
+                                                      (uint4*)out16, out24, (unsigned long long*)first_fail,
+                                                      (unsigned long long*)bad_char, c->f, cfg(c, s, tbound))
+                          : amph::launch_rv_b64_seg(tx, n, woff, toff, K, grid, (uint4*)out16,
+                                                    (unsigned long long*)first_fail,
+                                                    (unsigned long long*)bad_char, c->f, cfg(c, s, tbound));
+    return e == hipSuccess ? AMPH_OK : hip_fail(e, masked ? "k_mask_b64_seg" : "k_rv_b64_seg");
+  }
+  if (int st = check_wire_tables(woff, toff, K, nchars)) return st;
+  const size_t T = woff[K];
+  if (T) {
+    for (int j = 0; j < n; ++j)
+      for (int k = 0; k < 5; ++k)
+        if (!b64_field(odos[j], k)) return fail(AMPH_E_PARAM, "null ODO field text");
+    if ((!masked && !out16) || (masked && !secrets)) return fail(AMPH_E_PARAM, "null secrets/output");
+  }
+  WirePieces io;
+  io.text = [&](int j, int k, size_t o) { return b64_field(odos[j], k) + toff[o]; };
+  io.secrets = [&](size_t o) { return secrets + 16 * woff[o]; };
+  io.out16 = [&](size_t o) { return out16 + 16 * woff[o]; };
+  io.out24 = [&](size_t o) { return out24 + 24 * woff[o]; };
+  const size_t used = toff[K - 1] + amph::wire_text_chars(woff[K] - woff[K - 1]);  // the last text's end
+  return wire_batch_host(c, n, K, woff, toff, used, masked, out16 != nullptr, out24 != nullptr, io, first_fail,
+                         bad_char);
+}
+
+// Both gathered calls: odos[o * n + j], one words[o] per object.
+int wire_batch_call(amph_ctx* c, const amph_odo_b64* odos, int n, size_t K, const size_t* words, bool masked,
+                    const uint8_t* const* secrets, uint8_t* const* out16, char* const* out24,
+                    int64_t* first_fail, int64_t* bad_char, uint32_t flags) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  if (flags) return fail(AMPH_E_PARAM, "the gathered batch calls take host memory only (flags must be 0)");
+  if (K == 0) return AMPH_OK;
+  if (int st = wire_batch_parties(odos, n)) return st;
+  if (!words || !first_fail || !bad_char || (!masked && !out16) || (masked && !secrets))
+    return fail(AMPH_E_PARAM, "null pointer array or verdict array");
+  std::vector<uint64_t> woff(K + 1, 0), toff(K, 0);
+  size_t chars = 0;
+  for (size_t o = 0; o < K; ++o) {
+    const size_t nc = amph::wire_text_chars(words[o]);
+    for (int j = 0; j < n; ++j) {
+      const amph_odo_b64& t = odos[o * (size_t)n + j];
+      if (t.nchars != nc)
+        return fail(AMPH_E_LEN, "object " + std::to_string(o) + ", party " + std::to_string(j) +
+                                    ": base64 fields of " + std::to_string(t.nchars) + " characters, expected " +
+                                    std::to_string(nc) + " for " + std::to_string(words[o]) + " words");
+      for (int k = 0; k < 5 && words[o]; ++k)
+        if (!b64_field(t, k)) return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null ODO field text");
+    }
+    if (words[o] && ((out16 && !out16[o]) || (out24 && !out24[o]) || (masked && !secrets[o])))
+      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null secrets/output");
+    woff[o + 1] = woff[o] + words[o];
+    toff[o] = chars;
+    chars += amph::wire_slot_chars(words[o]);
+  }
+  WirePieces io;
+  io.text = [&](int j, int k, size_t o) { return b64_field(odos[o * (size_t)n + j], k); };
+  io.secrets = [&](size_t o) { return secrets[o]; };
+  io.out16 = [&](size_t o) { return out16[o]; };
+  io.out24 = [&](size_t o) { return out24[o]; };
+  return wire_batch_host(c, n, K, woff.data(), toff.data(), chars, masked, out16 != nullptr, out24 != nullptr, io,
+                         first_fail, bad_char);
+}
+}  // namespace
+
+extern "C" {
+
+size_t amph_wire_slot_chars(size_t words) { return amph::wire_slot_chars(words); }
+
+uint64_t amph_wire_batch_copies(const amph_ctx* c) {
+  if (!c) return 0;
+  return (c->sub.empty() ? c : c->sub[0])->wire_copies.load(std::memory_order_relaxed);
+}
+
+int amph_recombine_verify_b64_packed(amph_ctx* c, const amph_odo_b64* odos, int n, const uint64_t* word_offsets,
+                                     const uint64_t* text_offsets, size_t n_objects, uint8_t* out_secrets,
+                                     int64_t* first_fail, int64_t* bad_char, uint32_t flags, void* stream) {
+  return wire_packed_call(c, odos, n, word_offsets, text_offsets, n_objects, false, nullptr, out_secrets, nullptr,
+                          first_fail, bad_char, flags, stream);
+}
+
+int amph_mask_input_b64_packed(amph_ctx* c, const amph_odo_b64* odos, int n, const uint64_t* word_offsets,
+                               const uint64_t* text_offsets, size_t n_objects, const uint8_t* secrets,
+                               uint8_t* out_masked16, char* out_records24, int64_t* first_fail, int64_t* bad_char,
+                               uint32_t flags, void* stream) {
+  return wire_packed_call(c, odos, n, word_offsets, text_offsets, n_objects, true, secrets, out_masked16,
+                          out_records24, first_fail, bad_char, flags, stream);
+}
+
+int amph_recombine_verify_b64_batch(amph_ctx* c, const amph_odo_b64* odos, int n, size_t n_objects,
+                                    const size_t* words, uint8_t* const* out_secrets, int64_t* first_fail,
+                                    int64_t* bad_char, uint32_t flags) {
+  return wire_batch_call(c, odos, n, n_objects, words, false, nullptr, out_secrets, nullptr, first_fail, bad_char,
+                         flags);
+}
+
+int amph_mask_input_b64_batch(amph_ctx* c, const amph_odo_b64* odos, int n, size_t n_objects, const size_t* words,
+                              const uint8_t* const* secrets, uint8_t* const* out_masked16,
+                              char* const* out_records24, int64_t* first_fail, int64_t* bad_char, uint32_t flags) {
+  return wire_batch_call(c, odos, n, n_objects, words, true, secrets, out_masked16, out_records24, first_fail,
+                         bad_char, flags);
 }
 
 }  // extern "C"

@@ -215,6 +215,20 @@ hipError_t launch_mask_json(const TextSet& tx, int n, size_t words, size_t nchar
                             unsigned long long* first_fail, unsigned long long* bad, const Fp& f,
                             const LaunchCfg& c);
 
+// K_RV / K_MASK from the wire for many objects in one launch (wire.hip, "the
+// slotted text layout"; wiretiles.hpp): object o's texts start toff[o]
+// characters into every field buffer and its words are packed on
+// woff[n_objects + 1]; ff / bad are arrays of n_objects verdict words with
+// object-local indices.  grid: wire_tile_grid(T, n_objects) workgroups, or
+// any upper bound of it (surplus workgroups exit).  One secret per mask word.
+hipError_t launch_rv_b64_seg(const TextSet& tx, int n, const uint64_t* woff, const uint64_t* toff,
+                             size_t n_objects, size_t grid, uint4* out_y, unsigned long long* first_fail,
+                             unsigned long long* bad, const Fp& f, const LaunchCfg& c);
+hipError_t launch_mask_b64_seg(const TextSet& tx, int n, const uint64_t* woff, const uint64_t* toff,
+                               size_t n_objects, size_t grid, const uint4* secrets, uint4* out16, char* out24,
+                               unsigned long long* first_fail, unsigned long long* bad, const Fp& f,
+                               const LaunchCfg& c);
+
 // Small host calls: copy n verdict words from device memory to page-locked
 // host memory and reset them to kNoFail (one 64-lane workgroup).
 hipError_t launch_take_words(unsigned long long* dev, unsigned long long* host, int n, hipStream_t s);

@@ -10,6 +10,7 @@
 
 #include "b64.hpp"
 #include "devio.hpp"
+#include "wiretiles.hpp"
 
 namespace amph {
 namespace {
@@ -95,16 +96,34 @@ __device__ __forceinline__ void bad_unit(const uint4 v, int j, int k, size_t nch
   atomicMin(bad, (unsigned long long)((size_t)(5 * j + k) * nchars + 16 * unit + fb));
 }
 
-template <int NP, bool BIG, bool FAST, int BS>
+// The per-character path of one unit with its report (party j, field k in
+// ODO order, then the offset).
+__device__ __forceinline__ void slow_unit(const char* t, size_t unit, size_t nchars, uint32_t pad, int j, int k,
+                                          uint32_t (&o)[3], unsigned long long* bad) {
+  const uint32_t fb = dec_unit_slow(t, unit, nchars, pad, o);
+  if (fb != 0xFFFFFFFFu)
+    atomicMin(bad, (unsigned long long)((size_t)(5 * j + k) * nchars + 16 * unit + fb));
+}
+
+// toff: the texts start this many characters (a multiple of 16) into every
+// field buffer (the segmented kernels' slot offset).  MIXED (with FAST): the
+// tile that holds a text's end, lane by lane -- a lane whose unit ends at
+// least 4 characters before nchars (lane_fast) loads and decodes as the fast
+// path does, a lane whose unit starts at or past nchars contributes zero
+// bits (what the per-character path decodes there) without decoding, and the
+// one or two lanes in between take the per-character path and read nothing
+// past the text.
+template <int NP, bool BIG, bool FAST, int BS, bool MIXED = false>
 __device__ __forceinline__ void wire_fields(const TextSet& tx, int n, size_t nchars, uint32_t pad,
                                             size_t words, uint4 (&raw)[5][NP > 0 ? NP : 1],
                                             uint32_t (*lds)[3 * BS], W4 (&acc)[5],
                                             unsigned long long* bad, const Fp& f, size_t tile,
-                                            const uint8_t* lutp) {
+                                            const uint8_t* lutp, size_t toff = 0, bool lane_fast = true) {
   constexpr int G = WireGroups<NP>::G, NB = WireGroups<NP>::bufs;
   const size_t unit = tile * BS + threadIdx.x;
   const size_t word = tile * Wire<BS>::words + threadIdx.x;
   const bool consumer = threadIdx.x < Wire<BS>::words && word < words;
+  const bool lane_past = MIXED && 16 * unit >= nchars;  // the whole unit lies past the text: zero bits
   const int np = NP > 0 ? NP : n;
   int slot = 0;  // LDS buffer of the next field
 #pragma unroll
@@ -116,21 +135,32 @@ __device__ __forceinline__ void wire_fields(const TextSet& tx, int n, size_t nch
       if constexpr (FAST && NP > 0) {
         if constexpr (kWirePrefetch > 0) {
           const int ahead = k * NP + j + kWirePrefetch;
-          if (ahead < 5 * NP)
-            raw[ahead / NP][ahead % NP] = ld(reinterpret_cast<const uint4*>(tx.t[ahead / NP][ahead % NP]) + unit);
+          if (ahead < 5 * NP && (!MIXED || lane_fast))
+            raw[ahead / NP][ahead % NP] =
+                ld(reinterpret_cast<const uint4*>(tx.t[ahead / NP][ahead % NP] + toff) + unit);
         }
-        uint32_t badb = 0;  // the per-unit branch also bounds the LDS reads' live ranges: one
-        dec_unit16_lut(raw[k][j], o, badb, lutp);  // check after the last field took 117-256 VGPRs
-        if (badb & 0x80u) bad_unit(raw[k][j], j, k, nchars, unit, bad);
+        if (!MIXED || lane_fast) {
+          uint32_t badb = 0;  // the per-unit branch also bounds the LDS reads' live ranges: one
+          dec_unit16_lut(raw[k][j], o, badb, lutp);  // check after the last field took 117-256 VGPRs
+          if (badb & 0x80u) bad_unit(raw[k][j], j, k, nchars, unit, bad);
+        } else if (lane_past) {
+          o[0] = o[1] = o[2] = 0;
+        } else {
+          slow_unit(tx.t[k][j] + toff, unit, nchars, pad, j, k, o, bad);
+        }
       } else if constexpr (FAST) {
-        const uint4 v = ld(reinterpret_cast<const uint4*>(tx.t[k][j]) + unit);
-        uint32_t badb = 0;
-        dec_unit16_lut(v, o, badb, lutp);
-        if (badb & 0x80u) bad_unit(v, j, k, nchars, unit, bad);
+        if (!MIXED || lane_fast) {
+          const uint4 v = ld(reinterpret_cast<const uint4*>(tx.t[k][j] + toff) + unit);
+          uint32_t badb = 0;
+          dec_unit16_lut(v, o, badb, lutp);
+          if (badb & 0x80u) bad_unit(v, j, k, nchars, unit, bad);
+        } else if (lane_past) {
+          o[0] = o[1] = o[2] = 0;
+        } else {
+          slow_unit(tx.t[k][j] + toff, unit, nchars, pad, j, k, o, bad);
+        }
       } else {
-        const uint32_t fb = dec_unit_slow(tx.t[k][j], unit, nchars, pad, o);
-        if (fb != 0xFFFFFFFFu)  // (party j, field k) in ODO order, then the offset
-          atomicMin(bad, (unsigned long long)((size_t)(5 * j + k) * nchars + 16 * unit + fb));
+        slow_unit(tx.t[k][j] + toff, unit, nchars, pad, j, k, o, bad);
       }
       uint32_t* l = lds[slot];
       l[3 * threadIdx.x] = o[0];
@@ -160,15 +190,16 @@ __device__ __forceinline__ void wire_fields(const TextSet& tx, int n, size_t nch
 }
 
 template <int NP, int BS>
-__device__ __forceinline__ void wire_load(const TextSet& tx, uint4 (&raw)[5][NP > 0 ? NP : 1], size_t tile) {
+__device__ __forceinline__ void wire_load(const TextSet& tx, uint4 (&raw)[5][NP > 0 ? NP : 1], size_t tile,
+                                          size_t toff = 0, bool lane_fast = true) {
   if constexpr (NP > 0) {
     const size_t unit = tile * BS + threadIdx.x;
 #pragma unroll
     for (int k = 0; k < 5; ++k)
 #pragma unroll
       for (int j = 0; j < NP; ++j)
-        if (kWirePrefetch == 0 || k * NP + j < kWirePrefetch)
-          raw[k][j] = ld(reinterpret_cast<const uint4*>(tx.t[k][j]) + unit);
+        if ((kWirePrefetch == 0 || k * NP + j < kWirePrefetch) && lane_fast)
+          raw[k][j] = ld(reinterpret_cast<const uint4*>(tx.t[k][j] + toff) + unit);
   }
 }
 
@@ -364,6 +395,126 @@ __global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_json(TextSet tx, int 
   mask_tile_out<NP, BS, true>(blockIdx.x, words, s, n_secrets, acc, nullptr, out_text, ff, lds, f);
 }
 
+// ---- many secrets per launch: the slotted text layout ---------------------------
+// K objects' texts in one launch (include/amphora_wire_batch.h): every one of
+// the 5N field buffers holds object o's own base64 text, its own '=' padding
+// included, at character offset toff[o] (a multiple of 16, the same in every
+// buffer); the objects' words are packed on woff[n_objects + 1] as in the
+// packed word calls.  A workgroup decodes one tile of ONE object
+// (wiretiles.hpp: which one, without a scan), so everything above applies with
+// that object's nchars / pad / words, the text pointers advanced by its slot
+// and the outputs by woff[o]; the verdict words are first_fail[o] / bad[o]
+// with object-local indices -- bit for bit what the single call on that object
+// alone reports.  Bytes of a buffer outside the texts are never read.
+//
+// The tile that holds a text's end is one per OBJECT here (1 in 6 at 1,000
+// words, every tile below 192): AMPH_WIRE_SEG_LANES = 1 decodes it lane by
+// lane (wire_fields' MIXED form: only the lanes that hold the final group
+// take the per-character path, the divergence stays in one wave), 0 takes the
+// whole tile through the per-character path as k_rv_b64 does (DESIGN.md
+// section 4c', "the last tile").
+#ifndef AMPH_WIRE_SEG_LANES
+#define AMPH_WIRE_SEG_LANES 1
+#endif
+
+struct SegTile {
+  size_t o, tile;  // the object and its tile
+  size_t w0, words, nchars, toff;
+  uint32_t pad;
+};
+
+// This workgroup's tile (wave-uniform: scalar loads only); false: none.  The
+// word range is clamped into [0, woff[n_objects]], so whatever the table holds
+// no output word past the packed arrays' T words is written.
+template <int BS>
+__device__ __forceinline__ bool seg_tile(const uint64_t* woff, const uint64_t* toff, size_t n_objects, SegTile& s) {
+  static_assert(Wire<BS>::words == kWireTileWords, "wiretiles.hpp's tile is this workgroup's");
+  const WireTile wt = wire_tile_find(woff, n_objects, blockIdx.x, Wire<BS>::words);
+  const uint64_t T = woff[n_objects];
+  const uint64_t a = woff[wt.object], b = woff[wt.object + 1];
+  const uint64_t w0 = a < T ? a : T, w1 = b < w0 ? w0 : (b < T ? b : T);
+  if (!wire_tile_real(wt.local, w1 - w0, Wire<BS>::words)) return false;
+  s.o = wt.object, s.tile = wt.local, s.w0 = w0, s.words = w1 - w0;
+  s.nchars = wire_text_chars(s.words);
+  s.pad = (uint32_t)((3 - (16 * s.words) % 3) % 3);
+  s.toff = toff[wt.object];
+  return true;
+}
+
+template <int NP, bool BIG, int BS>
+__device__ __forceinline__ void seg_fields(const TextSet& tx, int n, const SegTile& s,
+                                           uint4 (&raw)[5][NP > 0 ? NP : 1], uint32_t (*lds)[3 * BS],
+                                           W4 (&acc)[5], unsigned long long* bad, const Fp& f,
+                                           const uint8_t* lutp) {
+  const bool fast = (s.tile + 1) * Wire<BS>::chars + 4 <= s.nchars;
+  if (fast) {
+    wire_load<NP, BS>(tx, raw, s.tile, s.toff);
+    wire_fields<NP, BIG, true, BS>(tx, n, s.nchars, s.pad, s.words, raw, lds, acc, bad, f, s.tile, lutp, s.toff);
+  } else if constexpr (AMPH_WIRE_SEG_LANES) {
+    const bool lane_fast = 16 * (s.tile * BS + threadIdx.x + 1) + 4 <= s.nchars;
+    wire_load<NP, BS>(tx, raw, s.tile, s.toff, lane_fast);
+    wire_fields<NP, BIG, true, BS, true>(tx, n, s.nchars, s.pad, s.words, raw, lds, acc, bad, f, s.tile, lutp,
+                                         s.toff, lane_fast);
+  } else {
+    wire_fields<NP, BIG, false, BS>(tx, n, s.nchars, s.pad, s.words, raw, lds, acc, bad, f, s.tile, lutp, s.toff);
+  }
+}
+
+// k_rv_b64 over the slotted layout: out_y packed on woff, ff / bad arrays of
+// n_objects words.
+template <int NP, bool BIG, int BS>
+__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_rv_b64_seg(TextSet tx, int n, const uint64_t* woff,
+                                               const uint64_t* toff, size_t n_objects, uint4* out_y,
+                                               unsigned long long* ff, unsigned long long* bad, Fp f) {
+  __shared__ uint32_t lds[WireGroups<NP>::bufs < 2 ? 2 : WireGroups<NP>::bufs][3 * BS];
+  __shared__ uint32_t lutw[kLutBytes / 4];
+  uint8_t* lutp = reinterpret_cast<uint8_t*>(lutw);
+  SegTile s;
+  const bool real = seg_tile<BS>(woff, toff, n_objects, s);  // its table loads fly during the fill
+  b64_lut_fill(lutp);
+  __syncthreads();
+  if (!real) return;  // (the whole workgroup)
+  W4 acc[5];
+  uint4 raw[5][NP > 0 ? NP : 1];
+  seg_fields<NP, BIG, BS>(tx, n, s, raw, lds, acc, bad + s.o, f, lutp);
+  const size_t word = s.tile * Wire<BS>::words + threadIdx.x;
+  if (threadIdx.x < Wire<BS>::words) {  // whole waves
+    const bool in = word < s.words;
+    bool ok = true;
+    if (in) {
+      ok = (int)eq(mont_mul_v(acc[0], acc[1], f), acc[3]) & (int)eq(mont_mul_v(acc[2], acc[1], f), acc[4]);
+      st_out(out_y + s.w0 + word, redc(acc[0], f));
+    }
+    report_fail(in && !ok, word, ff + s.o);
+  }
+}
+
+// k_mask_b64 over the slotted layout: one secret per mask word, secrets /
+// out16 / out24 packed on woff.
+template <int NP, bool BIG, int BS>
+__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_b64_seg(TextSet tx, int n, const uint64_t* woff,
+                                                 const uint64_t* toff, size_t n_objects, const uint4* secrets,
+                                                 uint4* out16, char* out24, unsigned long long* ff,
+                                                 unsigned long long* bad, Fp f) {
+  constexpr int WW = Wire<BS>::words;
+  __shared__ uint32_t lds[WireGroups<NP>::bufs < 2 ? 2 : WireGroups<NP>::bufs][3 * BS];
+  __shared__ uint32_t lutw[kLutBytes / 4];
+  uint8_t* lutp = reinterpret_cast<uint8_t*>(lutw);
+  SegTile s;
+  const bool real = seg_tile<BS>(woff, toff, n_objects, s);  // its table loads fly during the fill
+  b64_lut_fill(lutp);
+  __syncthreads();
+  if (!real) return;  // (the whole workgroup)
+  W4 acc[5];
+  uint4 raw[5][NP > 0 ? NP : 1];
+  seg_fields<NP, BIG, BS>(tx, n, s, raw, lds, acc, bad + s.o, f, lutp);
+  const size_t word = s.tile * WW + threadIdx.x;
+  uint4 sec = make_uint4(0, 0, 0, 0);  // (after the decode, as k_mask_b64)
+  if (threadIdx.x < WW && word < s.words) sec = ld(secrets + s.w0 + word);
+  mask_tile_out<NP, BS>(s.tile, s.words, sec, s.words, acc, out16 ? out16 + s.w0 : nullptr,
+                        out24 ? out24 + 24 * s.w0 : nullptr, ff + s.o, lds, f);
+}
+
 
 }  // namespace
 
@@ -401,6 +552,33 @@ hipError_t launch_mask_json(const TextSet& tx, int n, size_t words, size_t nchar
   constexpr int BS = kWireBlock;
   const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
 #define L(NP, BIG) AMPH_LAUNCH((k_mask_json<NP, BIG, BS>), g, dim3(BS), c, tx, n, words, nchars, pad, secrets, n_secrets, out_text, ff, bad, f)
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
+#undef L
+  return hipGetLastError();
+}
+
+hipError_t launch_rv_b64_seg(const TextSet& tx, int n, const uint64_t* woff, const uint64_t* toff,
+                             size_t n_objects, size_t grid, uint4* out_y, unsigned long long* ff,
+                             unsigned long long* bad, const Fp& f, const LaunchCfg& c) {
+  if (grid == 0 || n_objects == 0) return hipSuccess;
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)grid);
+#define L(NP, BIG) AMPH_LAUNCH((k_rv_b64_seg<NP, BIG, BS>), g, dim3(BS), c, tx, n, woff, toff, n_objects, out_y, ff, bad, f)
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
+#undef L
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_b64_seg(const TextSet& tx, int n, const uint64_t* woff, const uint64_t* toff,
+                               size_t n_objects, size_t grid, const uint4* secrets, uint4* out16, char* out24,
+                               unsigned long long* ff, unsigned long long* bad, const Fp& f,
+                               const LaunchCfg& c) {
+  if (grid == 0 || n_objects == 0) return hipSuccess;
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)grid);
+#define L(NP, BIG) AMPH_LAUNCH((k_mask_b64_seg<NP, BIG, BS>), g, dim3(BS), c, tx, n, woff, toff, n_objects, secrets, out16, out24, ff, bad, f)
   if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
 #undef L
   return hipGetLastError();

@@ -2,6 +2,7 @@
 and what batching buys ("Packed calls").
 
     python tools/bench_batch.py [--reps R] [--out FILE]
+    python tools/bench_batch.py --wire [--variant-lib LIB] [--reps R] [--out FILE]
 
 GPU only (fails without a device).  Everything is warmed up, then timed in
 alternating order within this one process; one JSON line with the build id.
@@ -17,6 +18,20 @@ alternating order within this one process; one JSON line with the build id.
   Wall clock around the C ABI calls (prebuilt arguments).
 * worst case: the segmented kernels at 2^20 words with EVERY word failing
   (recorded, not bounded), beside k_rv / k_mask on the same input.
+
+--wire measures the many-secrets wire-text calls instead (DESIGN.md section
+4c', include/amphora_wire_batch.h), same method:
+
+* hot path: k_rv_b64 / k_mask_b64 on one text of 2^20 words x 2 parties (timed
+  twice per round: the spread) against k_rv_b64_seg / k_mask_b64_seg with 1
+  object, 1,024 objects of 1,024 words and 1,049 objects of 1,000 words.
+* last tile (with --variant-lib: a second library built from the same tree
+  with -DAMPH_WIRE_SEG_LANES=0, the whole-tile per-character path): the two
+  forms at 1,000-word and 100-word objects, the default form twice per round.
+* batching: 256 objects x 1,000 words x 2 parties, host mode, wall clock with
+  prebuilt arguments: the batch call, 256 single wire-text calls, and 5 n
+  field decodes per object followed by the packed word call; and the same
+  size in device mode (one packed call against 256 enqueued single calls).
 """
 import argparse
 import ctypes as C
@@ -41,6 +56,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+ap.add_argument("--wire", action="store_true", help="the many-secrets wire-text calls (section 4c')")
+ap.add_argument("--variant-lib", default=None, help="--wire: a library built with -DAMPH_WIRE_SEG_LANES=0")
 a = ap.parse_args()
 
 _lib = A._lib
@@ -86,6 +103,260 @@ def wall_ms(fn):
 
 def ratio(res, num, den):
     return round(res[num]["median_ms"] / res[den]["median_ms"], 4)
+
+
+def emit(result):
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+# ---------------------------------------------------------------- --wire
+def wire_mode():
+    F_DEV = _lib.AMPH_F_DEVICE
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    nchars_of, slot_of = _lib.wire_text_chars, _lib.wire_slot_chars
+
+    def ok(st, lib=L):
+        if st != 0:
+            raise RuntimeError(lib.amph_last_error().decode())
+
+    def slotted(field, K, WO):
+        """field (T, 16) device words -> one buffer with K objects' own base64
+        texts of WO words each ('=' padded), dense slots, '!' in the gaps."""
+        nb, nc, sl = 16 * WO, nchars_of(WO), slot_of(WO)
+        pad = -nb % 3
+        x = torch.nn.functional.pad(field[:K * WO].reshape(K, nb), (0, pad)).reshape(-1).contiguous()
+        enc = ctx.base64_encode(x).reshape(K, nc)
+        if pad:
+            enc[:, nc - pad:] = ord("=")
+        buf = torch.full((K, sl), ord("!"), dtype=torch.uint8, device="cuda")
+        buf[:, :nc] = enc
+        return buf.reshape(-1)
+
+    def b64_structs(bufs, nchars, off=0, ptr=lambda x: x.data_ptr()):
+        return (_lib._AmphOdoB64 * N)(*[_lib._AmphOdoB64(*[ptr(bufs[k][j]) + off for k in range(5)], nchars)
+                                        for j in range(N)])
+
+    def table(K, WO):
+        woff = torch.arange(0, K * WO + 1, WO, dtype=torch.int64, device="cuda")
+        toff = torch.arange(0, K * slot_of(WO), slot_of(WO), dtype=torch.int64, device="cuda")
+        return woff, toff
+
+    class Shape:  # K objects of WO words as slotted device texts + the call's arguments
+        def __init__(self, field_bufs, secrets, K, WO):
+            self.K, self.WO, self.T = K, WO, K * WO
+            self.bufs = [[slotted(field_bufs[k, j], K, WO) for j in range(N)] for k in range(5)]
+            self.arr = b64_structs(self.bufs, K * slot_of(WO))
+            self.woff, self.toff = table(K, WO)
+            self.sec = secrets
+            self.ff = torch.empty(K, dtype=torch.int64, device="cuda")
+            self.bad = torch.empty(K, dtype=torch.int64, device="cuda")
+            self.o16 = torch.empty((self.T, 16), dtype=torch.uint8, device="cuda")
+            self.o24 = torch.empty((self.T, 24), dtype=torch.uint8, device="cuda")
+
+        def rv(self, lib=L, h=None):
+            ok(lib.amph_recombine_verify_b64_packed(h or ctx._h, self.arr, N, self.woff.data_ptr(),
+                                                    self.toff.data_ptr(), self.K, self.o16.data_ptr(),
+                                                    self.ff.data_ptr(), self.bad.data_ptr(), F_DEV, stream), lib)
+
+        def mask(self, lib=L, h=None):
+            ok(lib.amph_mask_input_b64_packed(h or ctx._h, self.arr, N, self.woff.data_ptr(), self.toff.data_ptr(),
+                                              self.K, self.sec.data_ptr(), self.o16.data_ptr(), self.o24.data_ptr(),
+                                              self.ff.data_ptr(), self.bad.data_ptr(), F_DEV, stream), lib)
+
+        def clean(self):
+            torch.cuda.synchronize()
+            return bool((self.ff == _lib.AMPH_NO_FAILURE).all()) and bool((self.bad == _lib.AMPH_NO_FAILURE).all())
+
+    W = 1 << 20
+    WMAX = 1049 * 1000
+    _, buf, _ = ctx.synth_odos(11, N, WMAX, noncanon_permille=20)  # (5, N, WMAX, 16)
+    secrets = ctx.synth_words(12, WMAX)
+    result = {"tool": "bench_batch --wire", "build_id": _lib.check_build_id(),
+              "device": torch.cuda.get_device_name(0), "parties": N, "reps": a.reps, "warmup": a.warmup}
+
+    # hot path: the unsegmented kernels on one text against the segmented ones
+    one = Shape(buf, secrets, 1, W)  # one object: the single call's own text and layout
+    s1024, s1000 = Shape(buf, secrets, 1024, 1024), Shape(buf, secrets, 1049, 1000)
+    flat = b64_structs(one.bufs, nchars_of(W))
+    ff1 = torch.empty(1, dtype=torch.int64, device="cuda")
+    bad1 = torch.empty(1, dtype=torch.int64, device="cuda")
+
+    def rv_flat():
+        ok(L.amph_recombine_verify_b64(ctx._h, flat, N, W, one.o16.data_ptr(),
+                                       C.cast(C.c_void_p(ff1.data_ptr()), i64p),
+                                       C.cast(C.c_void_p(bad1.data_ptr()), i64p), F_DEV, stream))
+
+    def mask_flat():
+        ok(L.amph_mask_input_b64(ctx._h, flat, N, W, secrets.data_ptr(), W, one.o16.data_ptr(), one.o24.data_ptr(),
+                                 C.cast(C.c_void_p(ff1.data_ptr()), i64p),
+                                 C.cast(C.c_void_p(bad1.data_ptr()), i64p), F_DEV, stream))
+
+    hot = {}
+    for name, flat_fn, seg in (("k_rv_b64", rv_flat, "rv"), ("k_mask_b64", mask_flat, "mask")):
+        res = alternate({name + "_a": flat_fn,
+                         name + "_seg_1_object": getattr(one, seg),
+                         name + "_seg_1024x1024": getattr(s1024, seg),
+                         name + "_seg_1049x1000": getattr(s1000, seg),
+                         name + "_a2": flat_fn}, a.reps, a.warmup, kernel_ms)
+        assert one.clean() and s1024.clean() and s1000.clean() and int(ff1.item()) == _lib.AMPH_NO_FAILURE
+        per_word = lambda k, words: res[k]["median_ms"] / words  # noqa: E731
+        res["ratios"] = {
+            name + "_a2_over_a (spread)": ratio(res, name + "_a2", name + "_a"),
+            name + "_seg_1_object_over_flat": ratio(res, name + "_seg_1_object", name + "_a"),
+            name + "_seg_1024x1024_over_flat": ratio(res, name + "_seg_1024x1024", name + "_a"),
+            name + "_seg_1049x1000_over_flat, per word": round(
+                per_word(name + "_seg_1049x1000", s1000.T) / per_word(name + "_a", W), 4),
+        }
+        hot[name] = res
+    result["hot_path"] = {"words": W, "words_1049x1000": s1000.T, "timing": "kernel dispatch events", **hot}
+    del one, s1024, flat
+
+    # the last tile: lane by lane (this library) against the whole tile per character (--variant-lib)
+    if a.variant_lib:
+        V = C.CDLL(os.path.abspath(a.variant_lib))
+        V.amph_last_error.restype = C.c_char_p
+        V.amph_build_id.restype = C.c_char_p
+        for fn in ("amph_recombine_verify_b64_packed", "amph_mask_input_b64_packed", "amph_ctx_create",
+                   "amph_time_next_launch"):
+            getattr(V, fn).argtypes = getattr(L, fn).argtypes
+        vh = C.c_void_p()
+        ok(V.amph_ctx_create(_lib.le16(TEST_PRIME), _lib.le16(TEST_R), _lib.le16(TEST_RINV), 0, C.byref(vh)), V)
+
+        def timed(lib):
+            def measure(fn):
+                lib.amph_time_next_launch(ev[0].handle, ev[1].handle)
+                fn()
+                torch.cuda.synchronize()
+                return ev[0].elapsed_ms(ev[1])
+            return measure
+
+        s100 = Shape(buf, secrets, 10485, 100)
+        last = {}
+        for sname, sh in (("1000_words", s1000), ("100_words", s100)):
+            for seg in ("rv", "mask"):
+                rows = {"lanes_a": (L, lambda sh=sh, seg=seg: getattr(sh, seg)()),
+                        "tile": (V, lambda sh=sh, seg=seg: getattr(sh, seg)(V, vh)),
+                        "lanes_a2": (L, lambda sh=sh, seg=seg: getattr(sh, seg)())}
+                ts = {k: [] for k in rows}
+                for r in range(a.reps + a.warmup):
+                    for k, (lib, fn) in rows.items():
+                        t = timed(lib)(fn)
+                        if r >= a.warmup:
+                            ts[k].append(t)
+                res = {k: stats(v) for k, v in ts.items()}
+                assert sh.clean()
+                res["ratios"] = {"lanes_a2_over_a (spread)": ratio(res, "lanes_a2", "lanes_a"),
+                                 "tile_over_lanes": ratio(res, "tile", "lanes_a")}
+                last["%s_%s" % (seg, sname)] = res
+        result["last_tile"] = {"objects_of_1000_words": s1000.K, "objects_of_100_words": s100.K,
+                               "variant_build_id": V.amph_build_id().decode(),
+                               "timing": "kernel dispatch events", **last}
+        del s100
+    del s1000
+
+    # what batching buys: 256 objects x 1,000 words
+    K, WO = 256, 1000
+    nc, sl, T = nchars_of(WO), slot_of(WO), K * WO
+    sh = Shape(buf, secrets, K, WO)
+    hbufs = [[sh.bufs[k][j].cpu().numpy() for j in range(N)] for k in range(5)]
+    hsec = secrets[:T].cpu().numpy()
+    hptr = lambda x: x.ctypes.data  # noqa: E731
+    singles_h = [b64_structs(hbufs, nc, o * sl, hptr) for o in range(K)]
+    singles_d = [b64_structs(sh.bufs, nc, o * sl) for o in range(K)]
+    gathered = (_lib._AmphOdoB64 * (K * N))(*[s[j] for s in singles_h for j in range(N)])
+    words = (C.c_size_t * K)(*([WO] * K))
+    h16, h24 = np.empty((T, 16), np.uint8), np.empty((T, 24), np.uint8)
+    hff, hbad = np.full(K, -1, np.int64), np.full(K, -1, np.int64)
+    p16 = (C.c_void_p * K)(*[h16.ctypes.data + 16 * WO * o for o in range(K)])
+    p24 = (C.c_void_p * K)(*[h24.ctypes.data + 24 * WO * o for o in range(K)])
+    psec = (C.c_void_p * K)(*[hsec.ctypes.data + 16 * WO * o for o in range(K)])
+    at = lambda x, o: C.cast(C.c_void_p(x.ctypes.data + 8 * o), i64p)  # noqa: E731
+    dat = lambda x, o: C.cast(C.c_void_p(x.data_ptr() + 8 * o), i64p)  # noqa: E731
+    # decode-then-packed: 5 n decoded field arrays, then amph_*_packed on them
+    dec = np.empty((5, N, T, 16), np.uint8)
+    dec_odos = (_lib._AmphOdo * N)(*[_lib._AmphOdo(*[dec[k, j].ctypes.data for k in range(5)], 16 * T)
+                                     for j in range(N)])
+    offsets = np.arange(0, T + 1, WO, dtype=np.uint64)
+    nbytes = C.c_size_t()
+
+    def decode_all():
+        for o in range(K):
+            for j in range(N):
+                for k in range(5):
+                    ok(L.amph_base64_decode(ctx._h, hbufs[k][j].ctypes.data + o * sl, nc,
+                                            dec[k, j].ctypes.data + 16 * WO * o, C.byref(nbytes), None, 0, None))
+
+    def host_singles(masked):
+        for o in range(K):
+            if masked:
+                ok(L.amph_mask_input_b64(ctx._h, singles_h[o], N, WO, psec[o], WO, p16[o], p24[o], at(hff, o),
+                                         at(hbad, o), 0, None))
+            else:
+                ok(L.amph_recombine_verify_b64(ctx._h, singles_h[o], N, WO, p16[o], at(hff, o), at(hbad, o), 0,
+                                               None))
+
+    def dev_singles(masked):
+        for o in range(K):
+            if masked:
+                ok(L.amph_mask_input_b64(ctx._h, singles_d[o], N, WO, sh.sec.data_ptr() + 16 * WO * o, WO,
+                                         sh.o16.data_ptr() + 16 * WO * o, sh.o24.data_ptr() + 24 * WO * o,
+                                         dat(sh.ff, o), dat(sh.bad, o), F_DEV, stream))
+            else:
+                ok(L.amph_recombine_verify_b64(ctx._h, singles_d[o], N, WO, sh.o16.data_ptr() + 16 * WO * o,
+                                               dat(sh.ff, o), dat(sh.bad, o), F_DEV, stream))
+        torch.cuda.synchronize()
+
+    def synced(fn):
+        fn()
+        torch.cuda.synchronize()
+
+    i64 = lambda x: x.ctypes.data_as(i64p)  # noqa: E731
+    breps = max(5, a.reps // 2)
+    bat = alternate({
+        "host_256_recombine_verify_b64": lambda: host_singles(False),
+        "host_recombine_verify_b64_batch": lambda: ok(L.amph_recombine_verify_b64_batch(
+            ctx._h, gathered, N, K, words, p16, i64(hff), i64(hbad), 0)),
+        "host_decode_then_recombine_verify_packed": lambda: (decode_all(), ok(L.amph_recombine_verify_packed(
+            ctx._h, dec_odos, N, offsets.ctypes.data, K, h16.ctypes.data, hff.ctypes.data, 0, None))),
+        "host_256_mask_input_b64": lambda: host_singles(True),
+        "host_mask_input_b64_batch": lambda: ok(L.amph_mask_input_b64_batch(
+            ctx._h, gathered, N, K, words, psec, p16, p24, i64(hff), i64(hbad), 0)),
+        "host_decode_then_mask_input_packed": lambda: (decode_all(), ok(L.amph_mask_input_packed(
+            ctx._h, dec_odos, N, offsets.ctypes.data, K, hsec.ctypes.data, h16.ctypes.data, hff.ctypes.data, 0,
+            None))),
+        "device_256_recombine_verify_b64": lambda: dev_singles(False),
+        "device_recombine_verify_b64_packed": lambda: synced(sh.rv),
+        "device_256_mask_input_b64": lambda: dev_singles(True),
+        "device_mask_input_b64_packed": lambda: synced(sh.mask),
+    }, breps, 3, wall_ms)
+    assert list(hff) == [-1] * K and list(hbad) == [-1] * K and sh.clean()
+    bat["speedup"] = {
+        "host_recombine_verify_b64: singles / batch": ratio(bat, "host_256_recombine_verify_b64",
+                                                            "host_recombine_verify_b64_batch"),
+        "host_recombine_verify: decode + packed / batch": ratio(bat, "host_decode_then_recombine_verify_packed",
+                                                                "host_recombine_verify_b64_batch"),
+        "host_mask_input_b64: singles / batch": ratio(bat, "host_256_mask_input_b64", "host_mask_input_b64_batch"),
+        "host_mask_input: decode + packed / batch": ratio(bat, "host_decode_then_mask_input_packed",
+                                                          "host_mask_input_b64_batch"),
+        "device_recombine_verify_b64: singles / packed": ratio(bat, "device_256_recombine_verify_b64",
+                                                               "device_recombine_verify_b64_packed"),
+        "device_mask_input_b64: singles / packed": ratio(bat, "device_256_mask_input_b64",
+                                                         "device_mask_input_b64_packed"),
+    }
+    result["batching"] = {"objects": K, "words_per_object": WO, "field_decodes_per_object": 5 * N,
+                          "timing": "wall clock, one synchronise per side", "reps": breps, **bat}
+    emit(result)
+
+
+if a.wire:
+    wire_mode()
+    del ctx  # (destroyed while the library is still loaded)
+    sys.exit(0)
 
 
 # ---------------------------------------------------------------- hot path
