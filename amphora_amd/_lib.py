@@ -140,6 +140,16 @@ def _load():
     L.amph_mask_input_b64_packed.argtypes = [vp, vp, i32, vp, vp, sz, vp, vp, vp, vp, vp, u32, vp]
     L.amph_recombine_verify_b64_batch.argtypes = [vp, vp, i32, sz, C.POINTER(sz), pp, i64p, i64p, u32]
     L.amph_mask_input_b64_batch.argtypes = [vp, vp, i32, sz, C.POINTER(sz), pp, pp, pp, i64p, i64p, u32]
+    # include/amphora_upload_batch.h
+    L.amph_upload_slot_chars.restype = sz
+    L.amph_upload_slot_chars.argtypes = [sz]
+    L.amph_upload_batch_copies.restype = u64
+    L.amph_upload_batch_copies.argtypes = [vp]
+    L.amph_convert_share_json_packed.argtypes = [vp, vp, sz, vp, vp, sz, vp, C.c_char_p, i32, vp, vp, u32, vp]
+    L.amph_convert_share_json_batch.argtypes = [vp, pp, C.POINTER(sz), C.POINTER(sz), sz, pp, C.c_char_p, i32, pp,
+                                                i64p, u32]
+    L.amph_mask_input_json_packed.argtypes = [vp, vp, i32, vp, vp, sz, vp, vp, sz, vp, vp, vp, u32, vp]
+    L.amph_mask_input_json_batch.argtypes = [vp, vp, i32, sz, C.POINTER(sz), pp, pp, i64p, i64p, u32]
     return L
 
 
@@ -193,6 +203,10 @@ EXPORTED = ["amph_ctx_create", "amph_ctx_create_multi", "amph_ctx_device_count",
 EXPORTED_WIRE_BATCH = ["amph_wire_slot_chars", "amph_wire_batch_copies", "amph_recombine_verify_b64_packed",
                        "amph_mask_input_b64_packed", "amph_recombine_verify_b64_batch",
                        "amph_mask_input_b64_batch"]
+# what include/amphora_upload_batch.h declares
+EXPORTED_UPLOAD_BATCH = ["amph_upload_slot_chars", "amph_upload_batch_copies", "amph_convert_share_json_packed",
+                         "amph_convert_share_json_batch", "amph_mask_input_json_packed",
+                         "amph_mask_input_json_batch"]
 ODO_FIELD_NAMES = ("secretShares", "rShares", "vShares", "wShares", "uShares")
 
 
@@ -204,6 +218,16 @@ def wire_text_chars(words: int) -> int:
 def wire_slot_chars(words: int) -> int:
     """amph_wire_slot_chars: the text rounded up to whole 16-character units."""
     return int(lib.amph_wire_slot_chars(words))
+
+
+def masked_input_data_chars(words: int) -> int:
+    """Characters of the MaskedInput "data" array text of `words` compact records."""
+    return 37 * words + 1 if words else 2
+
+
+def upload_slot_chars(words: int) -> int:
+    """amph_upload_slot_chars: that text rounded up to whole 16-byte units."""
+    return int(lib.amph_upload_slot_chars(words))
 
 
 def wire_bad_char_message(bad: int, words: int) -> str:
@@ -887,6 +911,156 @@ class Context:
         words: (list of masked (W_o, 16) or None, list of records (W_o, 24) or
         None, first_fail[K], bad_char[K])."""
         return self._wire_batch(True, objects, words, secrets, records, raw, status)
+
+    # -- many MaskedInput uploads per launch (include/amphora_upload_batch.h) --------
+    def upload_batch_copies(self) -> int:
+        """amph_upload_batch_copies: host-device copies of the host-mode calls below."""
+        return int(lib.amph_upload_batch_copies(self._h))
+
+    @staticmethod
+    def _bytes_view(x):
+        if isinstance(x, str):
+            x = x.encode("utf-8")
+        if _is_dev(x):
+            a = x.reshape(-1)
+            if not a.is_contiguous():
+                raise ValueError("the text must be a contiguous uint8 tensor")
+            return a
+        if isinstance(x, (bytes, bytearray, memoryview)):
+            return np.frombuffer(bytes(x), np.uint8)
+        return np.ascontiguousarray(x, np.uint8).reshape(-1)
+
+    def _tables(self, like, K, tables, verdicts, accumulate):
+        """The offset tables and verdict arrays of a packed upload call where
+        `like` lives: (tables, verdicts, extra flags)."""
+        if _is_dev(like):
+            import torch
+            tables = [x if _is_dev(x) else torch.as_tensor(np.ascontiguousarray(x, np.uint64).view(np.int64))
+                      .to(like.device) for x in tables]
+            out = []
+            for v in verdicts:
+                if v is None:
+                    v = torch.empty(K, dtype=torch.int64, device=like.device)
+                    accumulate = False
+                elif v.numel() != K or v.dtype != torch.int64 or not v.is_cuda:
+                    raise ValueError("verdict arrays must be int64 device tensors with one entry per object")
+                out.append(v)
+            return tables, out, (AMPH_F_ACCUMULATE if accumulate else 0)
+        return ([np.ascontiguousarray(x, dtype=np.uint64) for x in tables],
+                [np.full(K, -1, dtype=np.int64) for _ in verdicts], 0)
+
+    def _upload_result(self, st, res, verdict, status):
+        """Per-object verdicts are the result (as _wire_batch_result)."""
+        msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
+        if not (st == AMPH_E_PARAM and not _is_dev(verdict) and (np.asarray(verdict) >= 0).any()):
+            self._check(st, allow_verify=True)
+        return res + ((st, msg),) if status else res
+
+    def convert_share_json_packed(self, texts, word_offsets, text_offsets, tuples32, mac_key: int,
+                                  use_zero_input_as_data: bool, out=None, bad_index=None, accumulate=False,
+                                  status=False):
+        """amph_convert_share_json_packed: K MaskedInput "data" array texts ->
+        K shares in one launch.  texts: one buffer (bytes / uint8 array, or a
+        1-D uint8 device tensor) holding object o's text at text_offsets[o]
+        (any alignment); tuples32 (T, 32) packed on word_offsets[K + 1].
+        Returns (shares (T, 32), bad_index[K]): host -- -1 or the offending
+        byte's offset inside the object's own text; device -- int64 tensor of
+        AMPH_NO_FAILURE / offset."""
+        a, t = self._bytes_view(texts), words_view(tuples32, 32)
+        flags, stream = self._mode(a, t)
+        n = a.numel() if _is_dev(a) else a.size
+        K = max(0, len(word_offsets) - 1)
+        if len(text_offsets) != K:
+            raise ValueError("one text offset per object, one more word offset")
+        (wo, to), (bad,), acc = self._tables(a, K, (word_offsets, text_offsets), (bad_index,), accumulate)
+        out = self._out(t, (t.shape[0], 32), out)
+        st = lib.amph_convert_share_json_packed(self._h, _ptr(a), n, _ptr(wo), _ptr(to), K, _ptr(t),
+                                                le16(mac_key % self.prime), int(use_zero_input_as_data), _ptr(out),
+                                                _ptr(bad), flags | acc, stream)
+        return self._upload_result(st, (out, bad), bad, status)
+
+    def convert_share_json_batch(self, texts, tuples, mac_key: int, use_zero_input_as_data: bool, status=False):
+        """amph_convert_share_json_batch: texts[o] (str / bytes) with
+        tuples[o] ((W_o, 32)), host memory.  Returns (list of (W_o, 32)
+        shares, bad_index[K]) -- per object what convert_share_json gives."""
+        K = len(texts)
+        if len(tuples) != K:
+            raise ValueError("one tuple array per text")
+        tv = [self._bytes_view(x) for x in texts]
+        tu = [words_view(x, 32) for x in tuples]
+        outs = [np.empty((x.shape[0], 32), np.uint8) for x in tu]
+        bad = np.full(K, -1, dtype=np.int64)
+        szs = lambda xs: (C.c_size_t * max(1, K))(*xs)  # noqa: E731
+        ptrs = lambda xs: (C.c_void_p * max(1, K))(*[x.ctypes.data for x in xs])  # noqa: E731
+        st = lib.amph_convert_share_json_batch(self._h, ptrs(tv), szs([x.size for x in tv]),
+                                               szs([x.shape[0] for x in tu]), K, ptrs(tu),
+                                               le16(mac_key % self.prime), int(use_zero_input_as_data), ptrs(outs),
+                                               bad.ctypes.data_as(C.POINTER(C.c_int64)), 0)
+        return self._upload_result(st, (outs, bad), bad, status)
+
+    def mask_input_json_packed(self, texts, word_offsets, text_offsets, secrets16, out_text_offsets=None,
+                               out_text=None, first_fail=None, bad_char=None, accumulate=False, status=False):
+        """amph_mask_input_json_packed: mask_input_b64_packed with every
+        object's records written as its framed "data" array text.  Object o's
+        text goes to out_text[out_text_offsets[o]:] (multiples of 16; default:
+        the dense layout of upload_slot_chars strides in a fresh buffer).
+        Returns (out_text uint8 buffer, out_text_offsets, first_fail[K],
+        bad_char[K])."""
+        arr, keep = self._text_structs(texts)
+        s = words_view(secrets16)
+        flags, stream = self._mode(s, *keep)
+        like = keep[0]
+        K = max(0, len(word_offsets) - 1)
+        if len(text_offsets) != K:
+            raise ValueError("one text offset per object, one more word offset")
+        if out_text_offsets is None:
+            wo_h = np.asarray(word_offsets.cpu() if _is_dev(word_offsets) else word_offsets, dtype=np.uint64)
+            strides = [upload_slot_chars(int(wo_h[o + 1] - wo_h[o])) for o in range(K)]
+            out_text_offsets = np.concatenate([[0], np.cumsum(strides)]).astype(np.uint64)[:K]
+            cap = int(sum(strides))
+        else:
+            cap = None
+        if out_text is None:
+            if cap is None:
+                raise ValueError("out_text_offsets of the caller's need the caller's out_text")
+            out_text = self._empty(like, (max(16, cap),))
+        cap = out_text.numel() if _is_dev(out_text) else out_text.size
+        (wo, to, oo), (ff, bad), acc = self._tables(like, K, (word_offsets, text_offsets, out_text_offsets),
+                                                    (first_fail, bad_char), accumulate)
+        st = lib.amph_mask_input_json_packed(self._h, arr, len(texts), _ptr(wo), _ptr(to), K, _ptr(s),
+                                             _ptr(out_text), cap, _ptr(oo), _ptr(ff), _ptr(bad), flags | acc, stream)
+        return self._upload_result(st, (out_text, oo, ff, bad), bad, status)
+
+    def mask_input_json_batch(self, objects, words, secrets, status=False):
+        """amph_mask_input_json_batch: mask_input_json for K secrets at once
+        (host strings / bytes): (list of K texts as bytes, first_fail[K],
+        bad_char[K])."""
+        K = len(objects)
+        n = len(objects[0]) if K else 1
+        arr = (_AmphOdoB64 * max(1, K * n))()
+        keep = []
+        for o, obj in enumerate(objects):
+            if len(obj) != n:
+                raise ValueError("every object needs the same number of parties")
+            a, ks = self._text_structs(obj)
+            if any(_is_dev(f) for f in ks):
+                raise ValueError("the batch calls take host buffers")
+            keep.append(ks)
+            for j in range(n):
+                arr[o * n + j] = a[j]
+        if len(secrets) != K:
+            raise ValueError("one secrets array per object")
+        sv = [words_view(x) for x in secrets]
+        for o in range(K):
+            _need(sv[o].shape[0] == int(words[o]), "object %d: one secret per input mask word" % o)
+        wd = (C.c_size_t * max(1, K))(*[int(w) for w in words])
+        outs = [np.empty(masked_input_data_chars(int(w)), np.uint8) for w in words]
+        ff, bad = np.full(K, -1, dtype=np.int64), np.full(K, -1, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        ptrs = lambda xs: (C.c_void_p * max(1, K))(*[x.ctypes.data for x in xs])  # noqa: E731
+        st = lib.amph_mask_input_json_batch(self._h, arr, n, K, wd, ptrs(sv), ptrs(outs), ff.ctypes.data_as(i64p),
+                                            bad.ctypes.data_as(i64p), 0)
+        return self._upload_result(st, ([x.tobytes() for x in outs], ff, bad), bad, status)
 
     # -- wire codec (base64 as Jackson writes byte[]) ---------------------------
     def base64_encode(self, data) -> bytes:

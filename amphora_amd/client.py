@@ -445,6 +445,34 @@ def create_masked_input_body(util: SecretShareUtil, secret: Secret, odo_bodies: 
     return '{"secretId":"%s","data":%s,"tags":%s}' % (secret.secret_id, data.decode("ascii"), tj)
 
 
+def create_masked_input_bodies(util: SecretShareUtil, secrets: Sequence[Secret], list_of_odo_bodies_lists):
+    """create_masked_input_body for K secrets in one launch
+    (amph_mask_input_json_batch): every "data" array text leaves the GPU
+    framed, no host pass frames K bodies.  One entry per secret, equal to
+    what create_masked_inputs_from_bodies returns for it: the MaskedInput JSON
+    body or the exception the single function raises."""
+    import json
+    from . import wire
+    if len(secrets) != len(list_of_odo_bodies_lists):
+        raise ValueError("one list of Input Mask ODO bodies per secret")
+    parsed = [_body_texts(b) for b in list_of_odo_bodies_lists]
+    n = next((len(t) for t, _ in parsed if t), 0)
+    regular = [t is not None and len(t) == n and secrets[o].size() == W for o, (t, W) in enumerate(parsed)]
+
+    def run(idx):
+        return util.context.mask_input_json_batch(
+            [parsed[o][0] for o in idx], [parsed[o][1] for o in idx],
+            [pack(secrets[o].data, util.prime) for o in idx])
+
+    def finish(o, data):
+        tj = json.dumps([wire._tag_obj(t) for t in secrets[o].tags], separators=(",", ":"))
+        return '{"secretId":"%s","data":%s,"tags":%s}' % (secrets[o].secret_id, data.decode("ascii"), tj)
+
+    return _wire_batch_outcomes(
+        util, parsed, regular, run, finish,
+        lambda o: create_masked_input_body(util, secrets[o], list_of_odo_bodies_lists[o]))
+
+
 def get_secret_data(util: SecretShareUtil, odos: Sequence[OutputDeliveryObject]) -> List[int]:
     """getSecret :206-217 arithmetic (alias of verify_output_delivery_objects)."""
     return verify_output_delivery_objects(util, odos)

@@ -2,7 +2,8 @@
 // error and device helpers, the word-array pipeline's types and the buffers
 // of one-shot host calls.  Everything here lives in one namespace of hidden
 // visibility: the library exports only what include/amphora.h and its
-// extension header include/amphora_wire_batch.h declare.
+// extension headers include/amphora_wire_batch.h and
+// include/amphora_upload_batch.h declare.
 //
 // Host-pointer calls stream the word arrays through the device in batches
 // (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
@@ -30,6 +31,7 @@
 
 #include "../../include/amphora.h"
 #include "../../include/amphora_wire_batch.h"
+#include "../../include/amphora_upload_batch.h"
 #include "host_stream.hpp"
 #include "kernels.hpp"
 
@@ -140,6 +142,7 @@ struct amph_ctx {
   // hipMemcpy calls that moved it (amph_wire_batch_copies)
   amph::PinnedBuf wire_img;
   std::atomic<uint64_t> wire_copies{0};
+  std::atomic<uint64_t> upload_copies{0};  // the same of amphora_upload_batch.h's calls (amph_upload_batch_copies)
   DevBuf xstage;  // host-mode staging of the exchange codec calls
   DevBuf xdev;    // device-mode scan scratch of the exchange codec calls
   hipEvent_t xdev_done = nullptr;  // the last device-mode exchange call's kernels

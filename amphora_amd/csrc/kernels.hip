@@ -23,6 +23,7 @@
 #include "b64.hpp"
 #include "decimal.hpp"
 #include "devio.hpp"
+#include "wiretiles.hpp"
 
 namespace amph {
 
@@ -274,6 +275,50 @@ __device__ __forceinline__ uint32_t json_record_bad(const uint32_t (&w)[10], boo
   return fb;
 }
 
+// One lane of k_conv_json / k_conv_json_seg, after the barrier: record
+// threadIdx.x of the window in txt (shift = the window's offset in its first
+// granule) is word i of its text, `words` long; checks its frame and
+// characters (and the text's leading '[' on word 0), reports into *bad with
+// offsets counted in that text, and turns the lane's tuple in buf into its share.
+template <bool BIG>
+__device__ __forceinline__ void conv_json_lane(const uint4* txt, uint4* buf, uint32_t shift, size_t i, size_t words,
+                                               const W4& alpha, int use_zero, unsigned long long* bad,
+                                               const Fp& f) {
+  const uint32_t* tw = reinterpret_cast<const uint32_t*>(txt);
+  const uint32_t o = shift + 1 + kJsonRec * threadIdx.x, d0 = o >> 2, sub = o & 3;
+  uint32_t d[11], w[10], x[6];
+#pragma unroll
+  for (int j = 0; j < 11; ++j) d[j] = tw[d0 + j];
+#pragma unroll
+  for (int j = 0; j < 10; ++j) w[j] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], sub);
+  // the 24 characters start at byte 10 of the record
+#pragma unroll
+  for (int q = 0; q < 6; ++q) x[q] = __builtin_amdgcn_alignbyte(w[q + 3], w[q + 2], 2);
+  const DecTabs tabs = dec_tabs_vgpr();
+  uint32_t ok = 0x80808080u, b[3];
+  dec_unit16_ok(make_uint4(x[0], x[1], x[2], x[3]), b, ok, tabs);
+  // as k_b64_unwords: the final "==" decode as 'A', the unused low bits of
+  // character 21 are ignored
+  const uint32_t v4 = dec4_values6(x[4], ok, tabs), v5 = dec4_values6((x[5] & 0xFFFFu) | 0x41410000u, ok, tabs);
+  const uint32_t g4 = (__builtin_amdgcn_udot4(v4, 0x00000140u, 0u, false) << 12) |
+                      __builtin_amdgcn_udot4(v4, 0x01400000u, 0u, false);
+  const uint32_t g5 = __builtin_amdgcn_udot4(v5, 0x00000140u, 0u, false) << 12;
+  const uint4 mr = make_uint4(b[0], b[1], b[2], __builtin_amdgcn_perm(g5, g4, 0x06000102u));
+  const bool last = i + 1 == words;
+  const bool framed = (int)(w[0] == 0x6176227Bu) & (int)(w[1] == 0x2265756Cu) & (int)((w[2] & 0xFFFFu) == 0x223Au) &
+                      (int)((w[8] >> 16) == 0x7D22u) & (int)((w[9] & 0xFFu) == (last ? 0x5Du : 0x2Cu));
+  if (!framed || ok != 0x80808080u || (x[5] >> 16) != 0x3D3Du) {
+    const uint32_t fb = json_record_bad(w, last);
+    if (fb != 0xFFFFFFFFu) atomicMin(bad, (unsigned long long)(1 + kJsonRec * i + fb));
+  }
+  if (i == 0 && ((tw[shift >> 2] >> (8 * (shift & 3))) & 0xFFu) != '[') atomicMin(bad, 0ULL);
+  const W4 m = canon<BIG>(w4(mr), f);
+  const W4 val = canon<BIG>(w4(buf[3 * threadIdx.x]), f);
+  const W4 mac = canon<BIG>(w4(buf[3 * threadIdx.x + 1]), f);
+  buf[3 * threadIdx.x] = u4(use_zero ? val : mod_add(val, m, f));
+  buf[3 * threadIdx.x + 1] = u4(mod_add(mac, mont_mul(m, alpha, f), f));
+}
+
 template <bool BIG>
 __global__ __launch_bounds__(kPairBlock) void k_conv_json(const char* text, const uint4* tuples,
                                                          size_t words, W4 alpha, int use_zero,
@@ -306,46 +351,89 @@ __global__ __launch_bounds__(kPairBlock) void k_conv_json(const char* text, cons
     if (q < (uint32_t)kJsonGran + 1) txt[q] = tv[r];
   }
   __syncthreads();
-  if (i < words) {
-    const uint32_t* tw = reinterpret_cast<const uint32_t*>(txt);
-    const uint32_t o = shift + 1 + kJsonRec * threadIdx.x, d0 = o >> 2, sub = o & 3;
-    uint32_t d[11], w[10], x[6];
-#pragma unroll
-    for (int j = 0; j < 11; ++j) d[j] = tw[d0 + j];
-#pragma unroll
-    for (int j = 0; j < 10; ++j) w[j] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], sub);
-    // the 24 characters start at byte 10 of the record
-#pragma unroll
-    for (int q = 0; q < 6; ++q) x[q] = __builtin_amdgcn_alignbyte(w[q + 3], w[q + 2], 2);
-    const DecTabs tabs = dec_tabs_vgpr();
-    uint32_t ok = 0x80808080u, b[3];
-    dec_unit16_ok(make_uint4(x[0], x[1], x[2], x[3]), b, ok, tabs);
-    // as k_b64_unwords: the final "==" decode as 'A', the unused low bits of
-    // character 21 are ignored
-    const uint32_t v4 = dec4_values6(x[4], ok, tabs), v5 = dec4_values6((x[5] & 0xFFFFu) | 0x41410000u, ok, tabs);
-    const uint32_t g4 = (__builtin_amdgcn_udot4(v4, 0x00000140u, 0u, false) << 12) |
-                        __builtin_amdgcn_udot4(v4, 0x01400000u, 0u, false);
-    const uint32_t g5 = __builtin_amdgcn_udot4(v5, 0x00000140u, 0u, false) << 12;
-    const uint4 mr = make_uint4(b[0], b[1], b[2], __builtin_amdgcn_perm(g5, g4, 0x06000102u));
-    const bool last = i + 1 == words;
-    const bool framed = (int)(w[0] == 0x6176227Bu) & (int)(w[1] == 0x2265756Cu) & (int)((w[2] & 0xFFFFu) == 0x223Au) &
-                        (int)((w[8] >> 16) == 0x7D22u) & (int)((w[9] & 0xFFu) == (last ? 0x5Du : 0x2Cu));
-    if (!framed || ok != 0x80808080u || (x[5] >> 16) != 0x3D3Du) {
-      const uint32_t fb = json_record_bad(w, last);
-      if (fb != 0xFFFFFFFFu) atomicMin(bad, (unsigned long long)(1 + kJsonRec * i + fb));
-    }
-    if (i == 0 && ((tw[shift >> 2] >> (8 * (shift & 3))) & 0xFFu) != '[') atomicMin(bad, 0ULL);
-    const W4 m = canon<BIG>(w4(mr), f);
-    const W4 val = canon<BIG>(w4(buf[3 * threadIdx.x]), f);
-    const W4 mac = canon<BIG>(w4(buf[3 * threadIdx.x + 1]), f);
-    buf[3 * threadIdx.x] = u4(use_zero ? val : mod_add(val, m, f));
-    buf[3 * threadIdx.x + 1] = u4(mod_add(mac, mont_mul(m, alpha, f), f));
-  }
+  if (i < words) conv_json_lane<BIG>(txt, buf, shift, i, words, alpha, use_zero, bad, f);
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     const size_t q = (size_t)r * kPairBlock + threadIdx.x;
     if (q < 2 * nblk) st_party(out + 2 * i0 + q, buf[(q >> 1) * 3 + (q & 1)]);
+  }
+}
+
+// k_conv_json over K texts in one launch (include/amphora_upload_batch.h):
+// object o's "data" array text starts toff[o] bytes into `text`, at ANY
+// alignment, and its tuples and shares are rows [woff[o], woff[o + 1]) of the
+// packed arrays.  A workgroup converts one tile of kPairBlock records of ONE
+// object (wiretiles.hpp at t = kPairBlock: which one, without a scan), so the
+// window's `shift` is the workgroup's own, `last`, the leading '[' and every
+// reported offset are counted in that object's text, and the verdict word is
+// bad[o].  An object of no words has no tile: its "[]" is checked by workgroup
+// g(o) = woff[o] / t + o, which is no other object's real tile (g is strictly
+// increasing and an empty object's successor starts at g(o) + 1 or later).
+// The word range is clamped into [0, woff[n_objects]] as seg_tile does, so
+// whatever a device table holds no share row past T is written and no verdict
+// word outside [0, n_objects).  Everything read from the tables is
+// wave-uniform (scalar loads); the tuple loads need the word table only, so
+// the text offset's load is in flight with them, and all of the workgroup's
+// global loads are issued before its first LDS write.
+template <bool BIG>
+__global__ __launch_bounds__(kPairBlock) void k_conv_json_seg(const char* text, const uint64_t* woff,
+                                                             const uint64_t* toff, size_t n_objects,
+                                                             const uint4* tuples, W4 alpha, int use_zero,
+                                                             uint4* out, unsigned long long* bad, Fp f) {
+  static_assert(kPairBlock == kConvTileWords, "wiretiles.hpp's K_CONV tile is this workgroup's");
+  __shared__ uint4 buf[3 * kPairBlock];
+  __shared__ uint4 txt[kJsonGran + 1];
+  const WireTile wt = wire_tile_find(woff, n_objects, blockIdx.x, kPairBlock);
+  const uint64_t T = woff[n_objects], a = woff[wt.object], b = woff[wt.object + 1];
+  const uint64_t t0 = toff[wt.object];
+  const uint64_t w0 = a < T ? a : T, w1 = b < w0 ? w0 : (b < T ? b : T);
+  const size_t words = (size_t)(w1 - w0);
+  bad += wt.object;
+  if (words == 0) {  // "[]", checked by the object's slot g(o) alone
+    if (wt.local == 0 && threadIdx.x < 2 && text[t0 + threadIdx.x] != (threadIdx.x ? ']' : '['))
+      atomicMin(bad, (unsigned long long)threadIdx.x);
+    return;
+  }
+  if (!wire_tile_real(wt.local, words, kPairBlock)) return;  // (the whole workgroup)
+  const size_t i0 = wt.local * kPairBlock, i = i0 + threadIdx.x;  // words of the object
+  const size_t nblk = min((size_t)kPairBlock, words - i0);
+  const uint4* tsrc = tuples + 2 * ((size_t)w0 + i0);
+  uint4 tu[2], tv[3];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const uint32_t q = r * kPairBlock + threadIdx.x;
+    tu[r] = make_uint4(0, 0, 0, 0);
+    if (q < 2 * (uint32_t)nblk) tu[r] = ld(tsrc + q);
+  }
+  const uintptr_t win = (uintptr_t)text + (size_t)t0 + (size_t)kJsonRec * i0;
+  const uint32_t shift = (uint32_t)(win & 15);
+  const uint4* src = reinterpret_cast<const uint4*>(win - shift);
+  const uint32_t ngran = (shift + kJsonRec * (uint32_t)nblk + 1 + 15) >> 4;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t q = r * kPairBlock + threadIdx.x;
+    tv[r] = make_uint4(0, 0, 0, 0);
+    if (q < ngran) tv[r] = ld(src + q);
+  }
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {  // (stage_tuples' layout)
+    const uint32_t q = r * kPairBlock + threadIdx.x;
+    if (q < 2 * (uint32_t)nblk) buf[(q >> 1) * 3 + (q & 1)] = tu[r];
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const uint32_t q = r * kPairBlock + threadIdx.x;
+    if (q < (uint32_t)kJsonGran + 1) txt[q] = tv[r];
+  }
+  __syncthreads();
+  if (i < words) conv_json_lane<BIG>(txt, buf, shift, i, words, alpha, use_zero, bad, f);
+  __syncthreads();
+  uint4* dst = out + 2 * ((size_t)w0 + i0);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const uint32_t q = r * kPairBlock + threadIdx.x;
+    if (q < 2 * (uint32_t)nblk) st_party(dst + q, buf[(q >> 1) * 3 + (q & 1)]);
   }
 }
 
@@ -858,6 +946,18 @@ hipError_t launch_convert_share_json(const char* text, const uint4* tuples, size
   const dim3 g((unsigned)(words ? (words + kPairBlock - 1) / kPairBlock : 1));  // (no words: "[]" is checked)
   if (f.big) AMPH_LAUNCH((k_conv_json<true>), g, dim3(kPairBlock), c, text, tuples, words, alpha, use_zero, out, bad, f);
   else AMPH_LAUNCH((k_conv_json<false>), g, dim3(kPairBlock), c, text, tuples, words, alpha, use_zero, out, bad, f);
+  return hipGetLastError();
+}
+
+hipError_t launch_convert_share_json_seg(const char* text, const uint64_t* woff, const uint64_t* toff,
+                                         size_t n_objects, size_t grid, const uint4* tuples, W4 alpha,
+                                         int use_zero, uint4* out, unsigned long long* bad, const Fp& f,
+                                         const LaunchCfg& c) {
+  if (grid == 0 || n_objects == 0) return hipSuccess;
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  const dim3 g((unsigned)grid);
+  if (f.big) AMPH_LAUNCH((k_conv_json_seg<true>), g, dim3(kPairBlock), c, text, woff, toff, n_objects, tuples, alpha, use_zero, out, bad, f);
+  else AMPH_LAUNCH((k_conv_json_seg<false>), g, dim3(kPairBlock), c, text, woff, toff, n_objects, tuples, alpha, use_zero, out, bad, f);
   return hipGetLastError();
 }
 

@@ -229,6 +229,23 @@ hipError_t launch_mask_b64_seg(const TextSet& tx, int n, const uint64_t* woff, c
                                unsigned long long* first_fail, unsigned long long* bad, const Fp& f,
                                const LaunchCfg& c);
 
+// Many MaskedInput uploads per launch (include/amphora_upload_batch.h).
+// Party side: K "data" array texts, object o's at text + toff[o] (any byte
+// alignment), its tuples and shares rows [woff[o], woff[o + 1]) of the packed
+// arrays; bad[o] = the smallest offending byte offset inside object o's own
+// text.  grid: wire_tile_grid(T, n_objects, 128) or any upper bound of it.
+hipError_t launch_convert_share_json_seg(const char* text, const uint64_t* woff, const uint64_t* toff,
+                                         size_t n_objects, size_t grid, const uint4* tuples, W4 alpha_mont,
+                                         int use_zero_input, uint4* out, unsigned long long* bad, const Fp& f,
+                                         const LaunchCfg& c);
+// Client side: launch_mask_b64_seg with object o's records written as its
+// framed "data" array text at out_text + ooff[o] (ooff[o] a multiple of 16;
+// "[]" for an object of no words).  grid: wire_tile_grid(T, n_objects).
+hipError_t launch_mask_json_seg(const TextSet& tx, int n, const uint64_t* woff, const uint64_t* toff,
+                                const uint64_t* ooff, size_t n_objects, size_t grid, const uint4* secrets,
+                                char* out_text, unsigned long long* first_fail, unsigned long long* bad,
+                                const Fp& f, const LaunchCfg& c);
+
 // Small host calls: copy n verdict words from device memory to page-locked
 // host memory and reset them to kNoFail (one 64-lane workgroup).
 hipError_t launch_take_words(unsigned long long* dev, unsigned long long* host, int n, hipStream_t s);

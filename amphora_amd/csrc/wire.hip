@@ -433,8 +433,8 @@ __device__ __forceinline__ bool seg_tile(const uint64_t* woff, const uint64_t* t
   const uint64_t T = woff[n_objects];
   const uint64_t a = woff[wt.object], b = woff[wt.object + 1];
   const uint64_t w0 = a < T ? a : T, w1 = b < w0 ? w0 : (b < T ? b : T);
+  s.o = wt.object, s.tile = wt.local, s.w0 = w0, s.words = w1 - w0;  // (also of a workgroup without a tile)
   if (!wire_tile_real(wt.local, w1 - w0, Wire<BS>::words)) return false;
-  s.o = wt.object, s.tile = wt.local, s.w0 = w0, s.words = w1 - w0;
   s.nchars = wire_text_chars(s.words);
   s.pad = (uint32_t)((3 - (16 * s.words) % 3) % 3);
   s.toff = toff[wt.object];
@@ -515,6 +515,44 @@ __global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_b64_seg(TextSet tx, i
                         out24 ? out24 + 24 * s.w0 : nullptr, ff + s.o, lds, f);
 }
 
+// k_mask_b64_seg with every object's masked words written as its own framed
+// "data" array text (mask_tile_out's JSON form, include/amphora_upload_batch.h):
+// object o's text goes to out_text + ooff[o], ooff[o] a multiple of 16, so the
+// image's 16-byte nontemporal runs stay aligned -- 37 x 192 is a multiple of
+// 16, every tile's records are whole runs from the object's own start on.
+// The '[' goes with the object's tile 0 and the ']' with its last record, the
+// final partial run leaves byte by byte: nothing past an object's ']' is
+// written.  An object of no words has no tile; its "[]" is written by
+// workgroup g(o) = woff[o] / 192 + o, which is no other object's real tile
+// (wiretiles.hpp).
+template <int NP, bool BIG, int BS>
+__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_json_seg(TextSet tx, int n, const uint64_t* woff,
+                                                  const uint64_t* toff, const uint64_t* ooff, size_t n_objects,
+                                                  const uint4* secrets, char* out_text, unsigned long long* ff,
+                                                  unsigned long long* bad, Fp f) {
+  constexpr int WW = Wire<BS>::words;
+  // (at least 3 buffers for the text image, as k_mask_json)
+  __shared__ __attribute__((aligned(16))) uint32_t lds[WireGroups<NP>::bufs < 3 ? 3 : WireGroups<NP>::bufs][3 * BS];
+  static_assert(3 * 3 * BS * 4 >= kJsonRec * WW + 4, "the text image fits the decode buffers");
+  __shared__ uint32_t lutw[kLutBytes / 4];
+  uint8_t* lutp = reinterpret_cast<uint8_t*>(lutw);
+  SegTile s;
+  const bool real = seg_tile<BS>(woff, toff, n_objects, s);  // its table loads fly during the fill
+  char* dst = out_text + ooff[s.o];
+  b64_lut_fill(lutp);
+  __syncthreads();
+  if (!real) {  // (the whole workgroup)
+    if (s.words == 0 && s.tile == 0 && threadIdx.x < 2) dst[threadIdx.x] = threadIdx.x ? ']' : '[';
+    return;
+  }
+  W4 acc[5];
+  uint4 raw[5][NP > 0 ? NP : 1];
+  seg_fields<NP, BIG, BS>(tx, n, s, raw, lds, acc, bad + s.o, f, lutp);
+  const size_t word = s.tile * WW + threadIdx.x;
+  uint4 sec = make_uint4(0, 0, 0, 0);  // (after the decode, as k_mask_b64)
+  if (threadIdx.x < WW && word < s.words) sec = ld(secrets + s.w0 + word);
+  mask_tile_out<NP, BS, true>(s.tile, s.words, sec, s.words, acc, nullptr, dst, ff + s.o, lds, f);
+}
 
 }  // namespace
 
@@ -579,6 +617,20 @@ hipError_t launch_mask_b64_seg(const TextSet& tx, int n, const uint64_t* woff, c
   constexpr int BS = kWireBlock;
   const dim3 g((unsigned)grid);
 #define L(NP, BIG) AMPH_LAUNCH((k_mask_b64_seg<NP, BIG, BS>), g, dim3(BS), c, tx, n, woff, toff, n_objects, secrets, out16, out24, ff, bad, f)
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
+#undef L
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_json_seg(const TextSet& tx, int n, const uint64_t* woff, const uint64_t* toff,
+                                const uint64_t* ooff, size_t n_objects, size_t grid, const uint4* secrets,
+                                char* out_text, unsigned long long* ff, unsigned long long* bad, const Fp& f,
+                                const LaunchCfg& c) {
+  if (grid == 0 || n_objects == 0) return hipSuccess;
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)grid);
+#define L(NP, BIG) AMPH_LAUNCH((k_mask_json_seg<NP, BIG, BS>), g, dim3(BS), c, tx, n, woff, toff, ooff, n_objects, secrets, out_text, ff, bad, f)
   if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
 #undef L
   return hipGetLastError();

@@ -31,6 +31,20 @@ AMPH_SEG_HD inline size_t wire_text_chars(size_t words) { return 4 * ((16 * word
 // the dense slotted layout's stride: the text rounded up to whole 16-byte units
 AMPH_SEG_HD inline size_t wire_slot_chars(size_t words) { return (wire_text_chars(words) + 15) & ~(size_t)15; }
 
+// The MaskedInput "data" array text of `words` records (37 bytes each, the
+// trailing ',' / ']' included, after one '['; "[]" for none) and its stride in
+// the dense 16-byte-aligned layout (include/amphora_upload_batch.h).  The
+// segmented K_CONV (k_conv_json_seg) applies the ownership rule below at
+// t = kConvTileWords, one workgroup's records; an object of no words has no
+// tile there but still a text, "[]", which workgroup g(o) handles: it exists
+// (g(o) < T / t + n_objects) and, g being strictly increasing with
+// g(o + 1) >= g(o) + 1, it is no other object's real tile.
+constexpr size_t kConvTileWords = 128;  // kPairBlock (kernels.hip asserts it)
+AMPH_SEG_HD inline size_t masked_input_data_chars(size_t words) { return words ? 37 * words + 1 : 2; }
+AMPH_SEG_HD inline size_t upload_slot_chars(size_t words) {
+  return (masked_input_data_chars(words) + 15) & ~(size_t)15;
+}
+
 // workgroups of the launch over T words in n_objects objects
 AMPH_SEG_HD inline size_t wire_tile_grid(uint64_t total_words, size_t n_objects, size_t t = kWireTileWords) {
   return (size_t)(total_words / t) + n_objects;

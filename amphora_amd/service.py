@@ -99,6 +99,55 @@ class SecretShareUtil:
         mi = wire.masked_input_from_json(self._ctx, raw.decode("utf-8"))
         return self.convert_to_secret_share(mi, mac_key, input_masks, use_zero_input_as_data)
 
+    def convert_masked_inputs_json(self, bodies, mac_key: str, list_of_input_masks,
+                                   use_zero_input_as_data: bool) -> list:
+        """convert_masked_input_json for K uploads in one launch
+        (amph_convert_share_json_batch): one entry per upload, the SecretShare
+        or the exception convert_masked_input_json raises for that upload.
+        Bodies whose "data" span is compact with one record per input mask go
+        through the one batch call; every other body -- another layout,
+        another count, a byte the kernel refuses -- takes
+        convert_masked_input_json itself and so keeps the reference's verdict
+        and message."""
+        import json
+        from . import wire
+        from .client import _outcome
+        if len(bodies) != len(list_of_input_masks):
+            raise ValueError("one list of input masks per body")
+        K = len(bodies)
+        out, parsed = [None] * K, {}
+        for o in range(K):
+            try:
+                masks = _tuples(list_of_input_masks[o], 32)
+                raw = bodies[o].encode("utf-8") if isinstance(bodies[o], str) else bytes(bodies[o])
+                span = wire.masked_input_data_span(raw)
+            except Exception:  # the single function raises it again as this upload's own
+                continue
+            if span is not None and span[1] + 1 - span[0] == _lib.masked_input_data_chars(masks.shape[0]):
+                parsed[o] = (raw[span[0]:span[1] + 1], masks, span[2])
+        idx = sorted(parsed)
+        if idx:
+            shares, bad = self._ctx.convert_share_json_batch([parsed[o][0] for o in idx],
+                                                             [parsed[o][1] for o in idx],
+                                                             int(mac_key) % self._ctx.prime, use_zero_input_as_data)
+
+            def finish(rest, share):
+                obj = json.loads(rest)
+                if obj.get("secretId") is None:
+                    raise IllegalArgumentException("secretId is marked non-null but is null")
+                return SecretShare(uuid.UUID(obj["secretId"]), share.tobytes(), list(obj.get("tags") or []))
+
+            for k, o in enumerate(idx):
+                if bad[k] < 0:
+                    out[o] = _outcome(finish, parsed[o][2], shares[k])
+                else:
+                    del parsed[o]
+        for o in range(K):
+            if o not in parsed:
+                out[o] = _outcome(self.convert_masked_input_json, bodies[o], mac_key, list_of_input_masks[o],
+                                  use_zero_input_as_data)
+        return out
+
 
 def _tuples(x, size):
     if isinstance(x, (list, tuple)):

@@ -3,6 +3,7 @@ and what batching buys ("Packed calls").
 
     python tools/bench_batch.py [--reps R] [--out FILE]
     python tools/bench_batch.py --wire [--variant-lib LIB] [--reps R] [--out FILE]
+    python tools/bench_batch.py --upload [--reps R] [--out FILE]
 
 GPU only (fails without a device).  Everything is warmed up, then timed in
 alternating order within this one process; one JSON line with the build id.
@@ -32,6 +33,18 @@ alternating order within this one process; one JSON line with the build id.
   prebuilt arguments: the batch call, 256 single wire-text calls, and 5 n
   field decodes per object followed by the packed word call; and the same
   size in device mode (one packed call against 256 enqueued single calls).
+
+--upload measures the many-uploads calls (DESIGN.md section 4c'',
+include/amphora_upload_batch.h), same method, one run on one board:
+
+* batching: 256 uploads x 1,000 words.  Client side at 2 and 3 parties: the
+  host batch call (amph_mask_input_json_batch) against 256 single host calls
+  (amph_mask_input_json), the device packed call against 256 enqueued single
+  device calls.  Party side: amph_convert_share_json_batch / _packed against
+  256 amph_convert_share_json calls, on the texts the client side wrote.
+* hot path at ONE object of the same 256,000 words, kernel time: k_mask_json
+  (twice per round: the spread) against k_mask_json_seg at 2 and 3 parties,
+  k_conv_json (twice) against k_conv_json_seg.
 """
 import argparse
 import ctypes as C
@@ -57,6 +70,7 @@ ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
 ap.add_argument("--wire", action="store_true", help="the many-secrets wire-text calls (section 4c')")
+ap.add_argument("--upload", action="store_true", help="the many-uploads calls (section 4c'')")
 ap.add_argument("--variant-lib", default=None, help="--wire: a library built with -DAMPH_WIRE_SEG_LANES=0")
 a = ap.parse_args()
 
@@ -114,6 +128,25 @@ def emit(result):
             fh.write(line + "\n")
 
 
+def slotted(field, K, WO):
+    """field (T, 16) device words -> one buffer with K objects' own base64
+    texts of WO words each ('=' padded), dense slots, '!' in the gaps."""
+    nb, nc, sl = 16 * WO, _lib.wire_text_chars(WO), _lib.wire_slot_chars(WO)
+    pad = -nb % 3
+    x = torch.nn.functional.pad(field[:K * WO].reshape(K, nb), (0, pad)).reshape(-1).contiguous()
+    enc = ctx.base64_encode(x).reshape(K, nc)
+    if pad:
+        enc[:, nc - pad:] = ord("=")
+    buf = torch.full((K, sl), ord("!"), dtype=torch.uint8, device="cuda")
+    buf[:, :nc] = enc
+    return buf.reshape(-1)
+
+
+def b64_structs(bufs, nchars, off=0, ptr=lambda x: x.data_ptr(), n=N):
+    return (_lib._AmphOdoB64 * n)(*[_lib._AmphOdoB64(*[ptr(bufs[k][j]) + off for k in range(5)], nchars)
+                                    for j in range(n)])
+
+
 # ---------------------------------------------------------------- --wire
 def wire_mode():
     F_DEV = _lib.AMPH_F_DEVICE
@@ -123,23 +156,6 @@ def wire_mode():
     def ok(st, lib=L):
         if st != 0:
             raise RuntimeError(lib.amph_last_error().decode())
-
-    def slotted(field, K, WO):
-        """field (T, 16) device words -> one buffer with K objects' own base64
-        texts of WO words each ('=' padded), dense slots, '!' in the gaps."""
-        nb, nc, sl = 16 * WO, nchars_of(WO), slot_of(WO)
-        pad = -nb % 3
-        x = torch.nn.functional.pad(field[:K * WO].reshape(K, nb), (0, pad)).reshape(-1).contiguous()
-        enc = ctx.base64_encode(x).reshape(K, nc)
-        if pad:
-            enc[:, nc - pad:] = ord("=")
-        buf = torch.full((K, sl), ord("!"), dtype=torch.uint8, device="cuda")
-        buf[:, :nc] = enc
-        return buf.reshape(-1)
-
-    def b64_structs(bufs, nchars, off=0, ptr=lambda x: x.data_ptr()):
-        return (_lib._AmphOdoB64 * N)(*[_lib._AmphOdoB64(*[ptr(bufs[k][j]) + off for k in range(5)], nchars)
-                                        for j in range(N)])
 
     def table(K, WO):
         woff = torch.arange(0, K * WO + 1, WO, dtype=torch.int64, device="cuda")
@@ -352,6 +368,192 @@ def wire_mode():
                           "timing": "wall clock, one synchronise per side", "reps": breps, **bat}
     emit(result)
 
+
+# ---------------------------------------------------------------- --upload
+def upload_mode():
+    F_DEV = _lib.AMPH_F_DEVICE
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    nchars_of, slot_of = _lib.wire_text_chars, _lib.wire_slot_chars
+    chars_of, stride_of = _lib.masked_input_data_chars, _lib.upload_slot_chars
+    NF = _lib.AMPH_NO_FAILURE
+
+    def ok(st):
+        if st != 0:
+            raise RuntimeError(L.amph_last_error().decode())
+
+    def synced(fn):
+        fn()
+        torch.cuda.synchronize()
+
+    K, WO = 256, 1000
+    T = K * WO
+    hptr = lambda x: x.ctypes.data  # noqa: E731
+    at = lambda x, o: C.cast(C.c_void_p(x.ctypes.data + 8 * o), i64p)  # noqa: E731
+    dat = lambda x, o: C.cast(C.c_void_p(x.data_ptr() + 8 * o), i64p)  # noqa: E731
+    i64 = lambda x: x.ctypes.data_as(i64p)  # noqa: E731
+    breps = max(5, a.reps // 2)
+    secrets = ctx.synth_words(12, T)
+    hsec = secrets.cpu().numpy()
+    words = (C.c_size_t * K)(*([WO] * K))
+    ostride, ochars = stride_of(WO), chars_of(WO)
+    result = {"tool": "bench_batch --upload", "build_id": _lib.check_build_id(),
+              "device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": a.warmup, "objects": K,
+              "words_per_object": WO, "batching_reps": breps,
+              "timing": {"batching": "wall clock, one synchronise per side", "hot_path": "kernel dispatch events"}}
+
+    # ---- client side: K secrets -> K framed texts, at 2 and 3 parties
+    client, texts_dev = {}, None
+    for n in (2, 3):
+        _, buf, _ = ctx.synth_odos(11, n, T, noncanon_permille=20)  # (5, n, T, 16)
+        nc, sl = nchars_of(WO), slot_of(WO)
+        bufs = [[slotted(buf[k, j], K, WO) for j in range(n)] for k in range(5)]
+        one = [[slotted(buf[k, j], 1, T) for j in range(n)] for k in range(5)]  # ONE object of T words
+        del buf
+        woff = torch.arange(0, T + 1, WO, dtype=torch.int64, device="cuda")
+        toff = torch.arange(0, K * sl, sl, dtype=torch.int64, device="cuda")
+        ooff = torch.arange(0, K * ostride, ostride, dtype=torch.int64, device="cuda")
+        out_d = torch.zeros(K * ostride, dtype=torch.uint8, device="cuda")
+        out_s = torch.zeros(K * ostride, dtype=torch.uint8, device="cuda")
+        ff, bad = (torch.empty(K, dtype=torch.int64, device="cuda") for _ in range(2))
+        packed = b64_structs(bufs, K * sl, n=n)
+        singles_d = [b64_structs(bufs, nc, o * sl, n=n) for o in range(K)]
+        hbufs = [[bufs[k][j].cpu().numpy() for j in range(n)] for k in range(5)]
+        singles_h = [b64_structs(hbufs, nc, o * sl, hptr, n=n) for o in range(K)]
+        gathered = (_lib._AmphOdoB64 * (K * n))(*[s[j] for s in singles_h for j in range(n)])
+        hout_b, hout_s = np.zeros(K * ostride, np.uint8), np.zeros(K * ostride, np.uint8)
+        hff, hbad = np.full(K, -1, np.int64), np.full(K, -1, np.int64)
+        pout_b = (C.c_void_p * K)(*[hout_b.ctypes.data + ostride * o for o in range(K)])
+        psec = (C.c_void_p * K)(*[hsec.ctypes.data + 16 * WO * o for o in range(K)])
+
+        def host_singles():
+            for o in range(K):
+                ok(L.amph_mask_input_json(ctx._h, singles_h[o], n, WO, psec[o], WO, hout_s.ctypes.data + ostride * o,
+                                          ochars, at(hff, o), at(hbad, o), 0, None))
+
+        def dev_singles():
+            for o in range(K):
+                ok(L.amph_mask_input_json(ctx._h, singles_d[o], n, WO, secrets.data_ptr() + 16 * WO * o, WO,
+                                          out_s.data_ptr() + ostride * o, ochars, dat(ff, o), dat(bad, o), F_DEV,
+                                          stream))
+            torch.cuda.synchronize()
+
+        def dev_packed():
+            ok(L.amph_mask_input_json_packed(ctx._h, packed, n, woff.data_ptr(), toff.data_ptr(), K,
+                                             secrets.data_ptr(), out_d.data_ptr(), K * ostride, ooff.data_ptr(),
+                                             ff.data_ptr(), bad.data_ptr(), F_DEV, stream))
+
+        bat = alternate({
+            "host_256_mask_input_json": host_singles,
+            "host_mask_input_json_batch": lambda: ok(L.amph_mask_input_json_batch(
+                ctx._h, gathered, n, K, words, psec, pout_b, i64(hff), i64(hbad), 0)),
+            "device_256_mask_input_json": dev_singles,
+            "device_mask_input_json_packed": lambda: synced(dev_packed),
+        }, breps, 3, wall_ms)
+        assert list(hff) == [-1] * K and list(hbad) == [-1] * K and bool((ff == NF).all()) and bool((bad == NF).all())
+        assert np.array_equal(hout_b, hout_s) and torch.equal(out_d, out_s) and np.array_equal(out_d.cpu().numpy(), hout_b)
+        bat["speedup"] = {
+            "host: singles / batch": ratio(bat, "host_256_mask_input_json", "host_mask_input_json_batch"),
+            "device: singles / packed": ratio(bat, "device_256_mask_input_json", "device_mask_input_json_packed"),
+        }
+        # hot path: one object of T words, the single call's own text and layout
+        flat = b64_structs(one, nchars_of(T), n=n)
+        w1 = torch.tensor([0, T], dtype=torch.int64, device="cuda")
+        z1 = torch.zeros(1, dtype=torch.int64, device="cuda")
+        t_flat = torch.zeros(stride_of(T), dtype=torch.uint8, device="cuda")
+        t_seg = torch.zeros(stride_of(T), dtype=torch.uint8, device="cuda")
+        ff1, bad1 = (torch.empty(1, dtype=torch.int64, device="cuda") for _ in range(2))
+
+        def k_flat():
+            ok(L.amph_mask_input_json(ctx._h, flat, n, T, secrets.data_ptr(), T, t_flat.data_ptr(), chars_of(T),
+                                      dat(ff1, 0), dat(bad1, 0), F_DEV, stream))
+
+        def k_seg():
+            ok(L.amph_mask_input_json_packed(ctx._h, flat, n, w1.data_ptr(), z1.data_ptr(), 1, secrets.data_ptr(),
+                                             t_seg.data_ptr(), stride_of(T), z1.data_ptr(), ff1.data_ptr(),
+                                             bad1.data_ptr(), F_DEV, stream))
+
+        hot = alternate({"k_mask_json_a": k_flat, "k_mask_json_seg_1_object": k_seg, "k_mask_json_a2": k_flat},
+                        a.reps, a.warmup, kernel_ms)
+        assert torch.equal(t_flat, t_seg) and int(ff1.item()) == NF and int(bad1.item()) == NF
+        hot["ratios"] = {"k_mask_json_a2_over_a (spread)": ratio(hot, "k_mask_json_a2", "k_mask_json_a"),
+                         "k_mask_json_seg_1_object_over_k_mask_json": ratio(hot, "k_mask_json_seg_1_object",
+                                                                            "k_mask_json_a")}
+        client["%d_parties" % n] = {"batching": bat, "hot_path_one_object_of_%d_words" % T: hot}
+        if n == 2:
+            texts_dev, ooff_dev, text_one = out_d, ooff, t_flat[:chars_of(T)]
+        del bufs, one, hbufs
+    result["client"] = client
+
+    # ---- party side: the K texts the client wrote -> K shares
+    tup = ctx.synth_words(13, 2 * T).reshape(T, 32)
+    htup, htexts = tup.cpu().numpy(), texts_dev.cpu().numpy()
+    key = _lib.le16(123456789)
+    woff = torch.arange(0, T + 1, WO, dtype=torch.int64, device="cuda")
+    sh_d, sh_s = (torch.zeros((T, 32), dtype=torch.uint8, device="cuda") for _ in range(2))
+    bad = torch.empty(K, dtype=torch.int64, device="cuda")
+    hsh_b, hsh_s = np.zeros((T, 32), np.uint8), np.zeros((T, 32), np.uint8)
+    hbad = np.full(K, -1, np.int64)
+    ptxt = (C.c_void_p * K)(*[htexts.ctypes.data + ostride * o for o in range(K)])
+    ptup = (C.c_void_p * K)(*[htup.ctypes.data + 32 * WO * o for o in range(K)])
+    pout = (C.c_void_p * K)(*[hsh_b.ctypes.data + 32 * WO * o for o in range(K)])
+    lens = (C.c_size_t * K)(*([ochars] * K))
+
+    def host_singles():
+        for o in range(K):
+            ok(L.amph_convert_share_json(ctx._h, ptxt[o], ochars, WO, ptup[o], key, 0,
+                                         hsh_s.ctypes.data + 32 * WO * o, at(hbad, o), 0, None))
+
+    def dev_singles():
+        for o in range(K):
+            ok(L.amph_convert_share_json(ctx._h, texts_dev.data_ptr() + ostride * o, ochars, WO,
+                                         tup.data_ptr() + 32 * WO * o, key, 0, sh_s.data_ptr() + 32 * WO * o,
+                                         dat(bad, o), F_DEV, stream))
+        torch.cuda.synchronize()
+
+    def dev_packed():
+        ok(L.amph_convert_share_json_packed(ctx._h, texts_dev.data_ptr(), K * ostride, woff.data_ptr(),
+                                            ooff_dev.data_ptr(), K, tup.data_ptr(), key, 0, sh_d.data_ptr(),
+                                            bad.data_ptr(), F_DEV, stream))
+
+    bat = alternate({
+        "host_256_convert_share_json": host_singles,
+        "host_convert_share_json_batch": lambda: ok(L.amph_convert_share_json_batch(
+            ctx._h, ptxt, lens, words, K, ptup, key, 0, pout, i64(hbad), 0)),
+        "device_256_convert_share_json": dev_singles,
+        "device_convert_share_json_packed": lambda: synced(dev_packed),
+    }, breps, 3, wall_ms)
+    assert list(hbad) == [-1] * K and bool((bad == NF).all())
+    assert np.array_equal(hsh_b, hsh_s) and torch.equal(sh_d, sh_s) and np.array_equal(sh_d.cpu().numpy(), hsh_b)
+    bat["speedup"] = {
+        "host: singles / batch": ratio(bat, "host_256_convert_share_json", "host_convert_share_json_batch"),
+        "device: singles / packed": ratio(bat, "device_256_convert_share_json", "device_convert_share_json_packed"),
+    }
+    w1 = torch.tensor([0, T], dtype=torch.int64, device="cuda")
+    z1 = torch.zeros(1, dtype=torch.int64, device="cuda")
+    bad1 = torch.empty(1, dtype=torch.int64, device="cuda")
+
+    def k_flat():
+        ok(L.amph_convert_share_json(ctx._h, text_one.data_ptr(), chars_of(T), T, tup.data_ptr(), key, 0,
+                                     sh_s.data_ptr(), dat(bad1, 0), F_DEV, stream))
+
+    def k_seg():
+        ok(L.amph_convert_share_json_packed(ctx._h, text_one.data_ptr(), chars_of(T), w1.data_ptr(), z1.data_ptr(), 1,
+                                            tup.data_ptr(), key, 0, sh_d.data_ptr(), bad1.data_ptr(), F_DEV, stream))
+
+    hot = alternate({"k_conv_json_a": k_flat, "k_conv_json_seg_1_object": k_seg, "k_conv_json_a2": k_flat},
+                    a.reps, a.warmup, kernel_ms)
+    assert torch.equal(sh_d, sh_s) and int(bad1.item()) == NF
+    hot["ratios"] = {"k_conv_json_a2_over_a (spread)": ratio(hot, "k_conv_json_a2", "k_conv_json_a"),
+                     "k_conv_json_seg_1_object_over_k_conv_json": ratio(hot, "k_conv_json_seg_1_object",
+                                                                        "k_conv_json_a")}
+    result["party"] = {"batching": bat, "hot_path_one_object_of_%d_words" % T: hot}
+    emit(result)
+
+
+if a.upload:
+    upload_mode()
+    del ctx  # (destroyed while the library is still loaded)
+    sys.exit(0)
 
 if a.wire:
     wire_mode()
