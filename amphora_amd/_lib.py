@@ -150,6 +150,11 @@ def _load():
                                                 i64p, u32]
     L.amph_mask_input_json_packed.argtypes = [vp, vp, i32, vp, vp, sz, vp, vp, sz, vp, vp, vp, u32, vp]
     L.amph_mask_input_json_batch.argtypes = [vp, vp, i32, sz, C.POINTER(sz), pp, pp, i64p, i64p, u32]
+    # include/amphora_respond_batch.h
+    L.amph_respond_batch_copies.restype = u64
+    L.amph_respond_batch_copies.argtypes = [vp]
+    L.amph_odo_fields_b64_packed.argtypes = [vp, vp, vp, vp, sz, vp, vp, u32, vp]
+    L.amph_odo_fields_b64_batch.argtypes = [vp, vp, sz, pp, vp, u32]
     return L
 
 
@@ -207,6 +212,8 @@ EXPORTED_WIRE_BATCH = ["amph_wire_slot_chars", "amph_wire_batch_copies", "amph_r
 EXPORTED_UPLOAD_BATCH = ["amph_upload_slot_chars", "amph_upload_batch_copies", "amph_convert_share_json_packed",
                          "amph_convert_share_json_batch", "amph_mask_input_json_packed",
                          "amph_mask_input_json_batch"]
+# what include/amphora_respond_batch.h declares
+EXPORTED_RESPOND_BATCH = ["amph_odo_fields_b64_packed", "amph_odo_fields_b64_batch", "amph_respond_batch_copies"]
 ODO_FIELD_NAMES = ("secretShares", "rShares", "vShares", "wShares", "uShares")
 
 
@@ -266,6 +273,11 @@ class _AmphOdo(C.Structure):
 class _AmphStats(C.Structure):  # amph_stats
     _fields_ = [(k, C.c_uint64) for k in ("kernel_launches", "pool_buffers", "pool_bytes",
                                            "device_workers", "worker_tasks")]
+
+
+class _AmphOdoB64Out(C.Structure):  # amph_odo_b64_out: five writable field buffers of nchars capacity each
+    _fields_ = [("secret_shares", C.c_void_p), ("r_shares", C.c_void_p), ("v_shares", C.c_void_p),
+                ("w_shares", C.c_void_p), ("u_shares", C.c_void_p), ("nchars", C.c_size_t)]
 
 
 class _AmphOdoB64(C.Structure):  # amph_odo_b64: one party's five base64 field texts
@@ -1061,6 +1073,97 @@ class Context:
         st = lib.amph_mask_input_json_batch(self._h, arr, n, K, wd, ptrs(sv), ptrs(outs), ff.ctypes.data_as(i64p),
                                             bad.ctypes.data_as(i64p), 0)
         return self._upload_result(st, ([x.tobytes() for x in outs], ff, bad), bad, status)
+
+    # -- many Output Delivery responses per launch (include/amphora_respond_batch.h) --
+    def respond_batch_copies(self) -> int:
+        """amph_respond_batch_copies: host-device copies of the host-mode calls below."""
+        return int(lib.amph_respond_batch_copies(self._h))
+
+    def odo_fields_b64_packed(self, fields5, word_offsets, text_offsets=None, out=None, reject=None):
+        """amph_odo_fields_b64_packed: K objects' five base64 field texts in one
+        launch.  fields5: the five packed word arrays ((T, 16) each, host arrays
+        or device tensors) in ODO order, the objects on word_offsets[K + 1];
+        object o's text of every field goes to text_offsets[o] of that field's
+        buffer (multiples of 16; default: the dense layout of wire_slot_chars
+        strides).  out: five uint8 buffers of one length (default: fresh ones
+        that end with the last slot); bytes outside the texts are not written.
+        reject: None or one int64 per object -- host: >= 0 rejects, device
+        tensor: != AMPH_NO_FAILURE rejects -- a rejected object's texts start
+        "!!!!".  Returns (the five buffers, text_offsets): what
+        recombine_verify_b64_packed takes as one party's texts and table."""
+        if len(fields5) != 5:
+            raise ValueError("five ODO fields")
+        lens = {byte_len(f) for f in fields5}
+        if len(lens) != 1:
+            raise AmphoraNativeError(AMPH_E_LEN, "The provided shares must be of the same length")
+        nbytes = lens.pop()
+        fs = [f if _is_dev(f) else np.ascontiguousarray(f, np.uint8).reshape(-1) for f in fields5]
+        flags, stream = self._mode(*fs)
+        like = fs[0]
+        K = max(0, len(word_offsets) - 1)
+        if text_offsets is None:
+            wo_h = [int(x) for x in (word_offsets.cpu() if _is_dev(word_offsets) else word_offsets)]
+            # (a decreasing table gets an empty slot here and its refusal from the library)
+            strides = [wire_slot_chars(max(0, wo_h[o + 1] - wo_h[o])) for o in range(K)]
+            text_offsets = np.concatenate([[0], np.cumsum(strides)]).astype(np.uint64)[:K]
+            cap = int(sum(strides))
+        else:
+            cap = None
+        if len(text_offsets) != K:
+            raise ValueError("one text offset per object, one more word offset")
+        if out is None:
+            if cap is None:
+                raise ValueError("text_offsets of the caller's need the caller's out buffers")
+            out = [self._empty(like, (max(16, cap),)) for _ in range(5)]
+        if len(out) != 5 or any(_is_dev(b) != _is_dev(like) for b in out):
+            raise ValueError("out: five buffers that live where the inputs live")
+        caps = {(b.numel() if _is_dev(b) else b.size) for b in out}
+        if len(caps) != 1:
+            raise ValueError("the five output buffers must have one length")
+        if _is_dev(like):
+            import torch
+            wo, to = [x if _is_dev(x) else torch.as_tensor(np.ascontiguousarray(x, np.uint64).view(np.int64))
+                      .to(like.device) for x in (word_offsets, text_offsets)]
+            if reject is not None and not (_is_dev(reject) and reject.dtype == torch.int64 and reject.numel() == K):
+                raise ValueError("reject must be an int64 device tensor with one entry per object")
+            rj = reject
+        else:
+            wo, to = [np.ascontiguousarray(x, dtype=np.uint64) for x in (word_offsets, text_offsets)]
+            rj = None if reject is None else np.ascontiguousarray(reject, dtype=np.int64)
+            if rj is not None and rj.size != K:
+                raise ValueError("one reject word per object")
+        odo = _AmphOdo(*[_ptr(f) for f in fs], nbytes)
+        ob = _AmphOdoB64Out(*[_ptr(b) for b in out], caps.pop())
+        self._check(lib.amph_odo_fields_b64_packed(self._h, C.byref(odo), _ptr(wo), _ptr(to), K, C.byref(ob),
+                                                   _ptr(rj), flags, stream))
+        return out, to
+
+    def odo_fields_b64_batch(self, list_of_fields5, reject=None):
+        """amph_odo_fields_b64_batch: fields5 (host word arrays) per object ->
+        per object its five base64 texts as bytes, one launch for all."""
+        K = len(list_of_fields5)
+        arr = (_AmphOdo * max(1, K))()
+        keep, outs = [], []
+        for o, f5 in enumerate(list_of_fields5):
+            if len(f5) != 5:
+                raise ValueError("five ODO fields per object")
+            lens = {byte_len(f) for f in f5}
+            if len(lens) != 1:
+                raise AmphoraNativeError(AMPH_E_LEN, "The provided shares must be of the same length")
+            fs = [np.ascontiguousarray(f, np.uint8).reshape(-1) for f in f5]
+            if any(_is_dev(f) for f in f5):
+                raise ValueError("the batch calls take host buffers")
+            keep.append(fs)
+            nbytes = lens.pop()
+            arr[o] = _AmphOdo(*[_ptr(f) for f in fs], nbytes)
+            outs.extend(np.empty(max(1, wire_text_chars(nbytes // 16)), np.uint8) for _ in range(5))
+        rj = None if reject is None else np.ascontiguousarray(reject, dtype=np.int64)
+        if rj is not None and rj.size != K:
+            raise ValueError("one reject word per object")
+        po = (C.c_void_p * max(1, 5 * K))(*[x.ctypes.data for x in outs])
+        self._check(lib.amph_odo_fields_b64_batch(self._h, arr, K, po, _ptr(rj), 0))
+        return [[outs[5 * o + k][:wire_text_chars(arr[o].nbytes // 16)].tobytes() for k in range(5)]
+                for o in range(K)]
 
     # -- wire codec (base64 as Jackson writes byte[]) ---------------------------
     def base64_encode(self, data) -> bytes:

@@ -2,8 +2,8 @@
 // error and device helpers, the word-array pipeline's types and the buffers
 // of one-shot host calls.  Everything here lives in one namespace of hidden
 // visibility: the library exports only what include/amphora.h and its
-// extension headers include/amphora_wire_batch.h and
-// include/amphora_upload_batch.h declare.
+// extension headers include/amphora_wire_batch.h,
+// include/amphora_upload_batch.h and include/amphora_respond_batch.h declare.
 //
 // Host-pointer calls stream the word arrays through the device in batches
 // (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
@@ -32,6 +32,7 @@
 #include "../../include/amphora.h"
 #include "../../include/amphora_wire_batch.h"
 #include "../../include/amphora_upload_batch.h"
+#include "../../include/amphora_respond_batch.h"
 #include "host_stream.hpp"
 #include "kernels.hpp"
 
@@ -143,6 +144,7 @@ struct amph_ctx {
   amph::PinnedBuf wire_img;
   std::atomic<uint64_t> wire_copies{0};
   std::atomic<uint64_t> upload_copies{0};  // the same of amphora_upload_batch.h's calls (amph_upload_batch_copies)
+  std::atomic<uint64_t> respond_copies{0};  // and of amphora_respond_batch.h's (amph_respond_batch_copies)
   DevBuf xstage;  // host-mode staging of the exchange codec calls
   DevBuf xdev;    // device-mode scan scratch of the exchange codec calls
   hipEvent_t xdev_done = nullptr;  // the last device-mode exchange call's kernels

@@ -3,6 +3,7 @@
 // and K_CONV from the MaskedInput "data" array text.
 #include "capi_internal.hpp"
 #include "wiretiles.hpp"
+#include "respondtiles.hpp"
 
 // ---- base64 wire codec ---------------------------------------------------------
 namespace {
@@ -1151,6 +1152,192 @@ int amph_mask_input_json_batch(amph_ctx* c, const amph_odo_b64* odos, int n, siz
   if (K && !flags && !out_texts) return fail(AMPH_E_PARAM, "null output text array");
   return wire_batch_call(c, odos, n, K, words, true, secrets, nullptr, nullptr, first_fail, bad_char, flags,
                          out_texts);
+}
+
+}  // extern "C"
+
+// ---- many Output Delivery responses per call (include/amphora_respond_batch.h) ----
+// The producer of the slotted field buffers the wire batch calls read: K
+// objects' five packed word arrays through k_odo_b64_seg (codec.hip,
+// respondtiles.hpp).  Host mode as the calls above: ONE page-locked image in
+// -- [word table | text table | reject | 5 word arrays] -- and one back -- the
+// five field buffers up to the last text's end -- scattered text by text, so
+// the caller's gaps stay untouched; a call that fits the small-call arena is
+// built and encoded there in place.  No verdicts: nothing to take back.
+namespace {
+const uint8_t* odo_words(const amph_odo& o, int k) {
+  const uint8_t* const f[5] = {o.secret_shares, o.r_shares, o.v_shares, o.w_shares, o.u_shares};
+  return f[k];
+}
+char* out_field(const amph_odo_b64_out& o, int k) {
+  char* const f[5] = {o.secret_shares, o.r_shares, o.v_shares, o.w_shares, o.u_shares};
+  return f[k];
+}
+
+// The host tables against T words and nchars characters: the wire batch
+// calls' rules, and then the kernel's own geometry -- no object's range is
+// clamped and no tile's text is clipped.
+int check_respond_tables(const uint64_t* woff, const uint64_t* toff, size_t K, uint64_t T, size_t nchars) {
+  if (int st = check_wire_tables(woff, toff, K, nchars)) return st;
+  if (woff[K] != T)
+    return fail(AMPH_E_PARAM, "word_offsets[" + std::to_string(K) + "] = " + std::to_string(woff[K]) +
+                                  " differs from the fields' " + std::to_string(T) + " words");
+  if (T > amph::kRespondMaxWords) return fail(AMPH_E_PARAM, "too many words for one call");
+  for (size_t o = 0; o < K; ++o) {
+    uint64_t w0, W;
+    amph::respond_object_words(woff, o, T, &w0, &W);
+    bool ok = w0 == woff[o] && W == woff[o + 1] - woff[o];
+    if (ok && W) {
+      const size_t last = (size_t)((W - 1) / amph::kWireTileWords);
+      const amph::RespondTile t = amph::respond_tile(woff, toff, o, last, T, nchars);
+      ok = t.words && t.store == t.chars && t.out_char == toff[o] + amph::kRespondTileChars * last &&
+           t.out_char + t.chars == toff[o] + amph::wire_text_chars(W);
+    }
+    if (!ok) return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": its tiles leave the arrays or the buffers");
+  }
+  return AMPH_OK;
+}
+
+struct RespondPieces {  // object o's words of field k, and where its text of field k goes
+  std::function<const uint8_t*(int, size_t)> in;
+  std::function<char*(int, size_t)> out;
+};
+
+// tables validated, T = woff[K] > 0; `used` = the last text's end
+int respond_host(amph_ctx* c, size_t K, const uint64_t* woff, const uint64_t* toff, size_t used,
+                 const RespondPieces& io, const int64_t* reject) {
+  const size_t T = woff[K];
+  if (!c->sub.empty()) c = c->sub[0];
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(use_device(c->device));
+  hipStream_t s;
+  if (int st = host_stream(c, 0, &s)) return st;
+  const size_t fchars = align256(used), fbytes = align256(16 * T);
+  const size_t tab_w = 0, tab_t = tab_w + align256(8 * (K + 1)), rej = tab_t + align256(8 * K);
+  const size_t wrd = rej + (reject ? align256(8 * K) : 0), in_bytes = wrd + 5 * fbytes;
+  const size_t txt = in_bytes, total = txt + 5 * fchars;
+  const bool small = small_call(c, total);
+  uint8_t *himg, *dimg;
+  if (small) {
+    if (c->small.ensure(total + 256) != hipSuccess) return fail(AMPH_E_NOMEM, "small-call arena");
+    himg = dimg = (uint8_t*)c->small.p;
+  } else {
+    if (c->wire_img.ensure(total) != hipSuccess) return fail(AMPH_E_NOMEM, "respond batch image");
+    if (dev_ensure(c, c->wire, total) != hipSuccess) return fail(AMPH_E_NOMEM, "respond staging");
+    himg = (uint8_t*)c->wire_img.p;
+    dimg = (uint8_t*)c->wire.p;
+  }
+  std::memcpy(himg + tab_w, woff, 8 * (K + 1));
+  std::memcpy(himg + tab_t, toff, 8 * K);
+  if (reject) {  // the device's convention: kNoFail = clean
+    unsigned long long* r = (unsigned long long*)(himg + rej);
+    for (size_t o = 0; o < K; ++o) r[o] = reject[o] >= 0 ? (unsigned long long)reject[o] : amph::kNoFail;
+  }
+  const uint8_t* din[5];
+  char* dout[5];
+  for (int k = 0; k < 5; ++k) {
+    for (size_t o = 0; o < K; ++o)
+      if (const size_t w = woff[o + 1] - woff[o])
+        std::memcpy(himg + wrd + k * fbytes + 16 * woff[o], io.in(k, o), 16 * w);
+    din[k] = dimg + wrd + k * fbytes;
+    dout[k] = (char*)(dimg + txt + k * fchars);
+  }
+  if (!small) {  // page-locked image, idle stream: one blocking copy (kPageableRule)
+    HIP_TRY(hipMemcpy(dimg, himg, in_bytes, hipMemcpyHostToDevice));
+    c->respond_copies.fetch_add(1, std::memory_order_relaxed);
+  }
+  hipError_t e = amph::launch_odo_b64_seg(din, dout, (const uint64_t*)(dimg + tab_w), (const uint64_t*)(dimg + tab_t),
+                                          K, amph::wire_tile_grid(T, K), T, used,
+                                          reject ? (const unsigned long long*)(dimg + rej) : nullptr, cfg(c, s, T));
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);
+    return hip_fail(e, "k_odo_b64_seg");
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (!small) {
+    HIP_TRY(hipMemcpy(himg + txt, dimg + txt, total - txt, hipMemcpyDeviceToHost));
+    c->respond_copies.fetch_add(1, std::memory_order_relaxed);
+  }
+  for (int k = 0; k < 5; ++k)
+    for (size_t o = 0; o < K; ++o)
+      if (const size_t nc = amph::wire_text_chars(woff[o + 1] - woff[o]))
+        std::memcpy(io.out(k, o), himg + txt + k * fchars + toff[o], nc);
+  return AMPH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+uint64_t amph_respond_batch_copies(const amph_ctx* c) {
+  if (!c) return 0;
+  return (c->sub.empty() ? c : c->sub[0])->respond_copies.load(std::memory_order_relaxed);
+}
+
+int amph_odo_fields_b64_packed(amph_ctx* c, const amph_odo* fields, const uint64_t* woff, const uint64_t* toff,
+                               size_t K, const amph_odo_b64_out* out, const int64_t* reject, uint32_t flags,
+                               void* stream) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  AMPH_NO_HOST_IO(flags);
+  if (flags & AMPH_F_ACCUMULATE) return fail(AMPH_E_PARAM, "AMPH_F_ACCUMULATE is not accepted by this call");
+  if (K == 0) return AMPH_OK;
+  if (!fields || !out || !woff || !toff) return fail(AMPH_E_PARAM, "null fields, output or offsets table");
+  if (fields->nbytes % 16) return fail(AMPH_E_LEN, "ODO field length must be a multiple of 16 bytes");
+  const size_t T = fields->nbytes / 16;
+  if (T == 0) return AMPH_OK;
+  for (int k = 0; k < 5; ++k)
+    if (!odo_words(*fields, k) || !out_field(*out, k)) return fail(AMPH_E_PARAM, "null ODO field or output text");
+  if (flags & AMPH_F_DEVICE) {
+    for (int k = 0; k < 5; ++k)
+      if (int st = check_dev_words({odo_words(*fields, k), out_field(*out, k)})) return st;
+    if (((uintptr_t)woff | (uintptr_t)toff | (uintptr_t)reject) & 7)
+      return fail(AMPH_E_PARAM, "device offset tables and verdict arrays must be 8-byte aligned");
+    if (!c->sub.empty()) c = c->sub[0];
+    HIP_TRY(use_device(c->device));
+    const uint8_t* din[5];
+    char* dout[5];
+    for (int k = 0; k < 5; ++k) {
+      din[k] = odo_words(*fields, k);
+      dout[k] = out_field(*out, k);
+    }
+    hipError_t e = amph::launch_odo_b64_seg(din, dout, woff, toff, K, amph::wire_tile_grid(T, K), T, out->nchars,
+                                            (const unsigned long long*)reject, cfg(c, (hipStream_t)stream, T));
+    return e == hipSuccess ? AMPH_OK : hip_fail(e, "k_odo_b64_seg");
+  }
+  if (int st = check_respond_tables(woff, toff, K, T, out->nchars)) return st;
+  RespondPieces io;
+  io.in = [&](int k, size_t o) { return odo_words(*fields, k) + 16 * woff[o]; };
+  io.out = [&](int k, size_t o) { return out_field(*out, k) + toff[o]; };
+  const size_t used = toff[K - 1] + amph::wire_text_chars(woff[K] - woff[K - 1]);  // the last text's end
+  return respond_host(c, K, woff, toff, used, io, reject);
+}
+
+int amph_odo_fields_b64_batch(amph_ctx* c, const amph_odo* odos, size_t K, char* const* out_fields,
+                              const int64_t* reject, uint32_t flags) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  if (flags) return fail(AMPH_E_PARAM, "the gathered batch calls take host memory only (flags must be 0)");
+  if (K == 0) return AMPH_OK;
+  if (!odos || !out_fields) return fail(AMPH_E_PARAM, "null ODO array or output text array");
+  std::vector<uint64_t> woff(K + 1, 0), toff(K, 0);
+  size_t chars = 0, used = 0;
+  for (size_t o = 0; o < K; ++o) {
+    if (odos[o].nbytes % 16)
+      return fail(AMPH_E_LEN, "object " + std::to_string(o) + ": ODO fields of " + std::to_string(odos[o].nbytes) +
+                                  " bytes, not a multiple of 16");
+    const size_t w = odos[o].nbytes / 16;
+    for (int k = 0; k < 5 && w; ++k)
+      if (!odo_words(odos[o], k) || !out_fields[5 * o + k])
+        return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null ODO field or output text");
+    woff[o + 1] = woff[o] + w;
+    toff[o] = chars;
+    if (w) used = chars + amph::wire_text_chars(w);
+    chars += amph::wire_slot_chars(w);
+  }
+  if (woff[K] == 0) return AMPH_OK;
+  if (woff[K] > amph::kRespondMaxWords) return fail(AMPH_E_PARAM, "too many words for one call");
+  RespondPieces io;
+  io.in = [&](int k, size_t o) { return odo_words(odos[o], k); };
+  io.out = [&](int k, size_t o) { return out_fields[5 * o + k]; };
+  return respond_host(c, K, woff.data(), toff.data(), used, io, reject);
 }
 
 }  // extern "C"

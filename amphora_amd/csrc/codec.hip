@@ -15,6 +15,7 @@
 
 #include "kernels.hpp"
 #include "b64.hpp"
+#include "respondtiles.hpp"
 
 namespace amph {
 
@@ -358,6 +359,85 @@ __global__ __launch_bounds__(kB64Block) void k_b64_encode_multi(B64Streams st, s
   }
 }
 
+// Many objects' five ODO fields in ONE launch (include/amphora_respond_batch.h):
+// each of the five packed word arrays holds T words, the concatenation of
+// n_objects objects on woff[n_objects + 1], and object o's base64 text of every
+// field goes toff[o] characters into that field's buffer of nchars characters.
+// Workgroup w owns the tile wire_tile_find gives it (wiretiles.hpp, t = 192
+// words = this workgroup's 256 units = 4,096 characters) or none;
+// respondtiles.hpp states what the tile reads and writes, clamped to [0, T]
+// and clipped to [0, nchars) whatever the device tables hold.  A whole tile is
+// k_b64_encode_blk's body; an object's last, partial tile goes unit by unit,
+// its final unit '='-padded and written byte-exactly.  reject (null or
+// n_objects words): an object whose word is not kNoFail gets "!!!!" as its
+// first four characters -- lane 0 of its tile 0 codes that unit, so the mark
+// leaves with the unit's own store (what k_poison_b64 does with a second
+// launch for a one-request session).
+// A workgroup codes its tile of all five fields in a loop: one table lookup
+// per five tiles.  One field per workgroup (blockIdx.y, as k_b64_encode_multi)
+// measured within 5 % at one object and 1.47x slower at 256 objects of 1,000
+// words ("Many Output Delivery responses' base64 fields in one
+// launch"; profiles/batch_respond_layout_ab.json).
+struct RespondFields {
+  const uint8_t* in[5];
+  char* out[5];
+};
+
+__device__ __forceinline__ void odo_b64_tile(const uint8_t* __restrict__ in, char* __restrict__ out,
+                                             const RespondTile& t, bool mark, uint32_t* lds) {
+  const uint8_t* src = in + 16 * t.in_word;  // 16-byte aligned with the array
+  char* dst = out + t.out_char;
+  if (t.whole()) {  // (uniform over the workgroup)
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    for (int q = threadIdx.x; q < 3 * kB64Block / 4; q += kB64Block) {
+      const uint4 v = ldnt4(s4 + q);
+      lds[4 * q] = v.x; lds[4 * q + 1] = v.y; lds[4 * q + 2] = v.z; lds[4 * q + 3] = v.w;
+    }
+    __syncthreads();
+    const uint32_t w[3] = {lds[3 * threadIdx.x], lds[3 * threadIdx.x + 1], lds[3 * threadIdx.x + 2]};
+    uint32_t g[4];
+    enc_unit12(w, g);
+    if (mark && threadIdx.x == 0) g[0] = 0x21212121u;  // "!!!!"
+    st16(dst + 16 * threadIdx.x, make_uint4(g[0], g[1], g[2], g[3]));
+    return;
+  }
+  // per unit: the tile's 16 t.words bytes are a whole number of dwords, so the
+  // final unit holds 4, 8 or 12 of them
+  const uint32_t nbytes = 16 * t.words, base = 12 * threadIdx.x;
+  if (base >= nbytes) return;
+  const uint32_t rem = nbytes - base < 12 ? nbytes - base : 12;
+  const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src + base);
+  const uint32_t w[3] = {s1[0], rem > 4 ? s1[1] : 0u, rem > 8 ? s1[2] : 0u};
+  uint32_t g[4];
+  enc_unit12(w, g);
+  if (mark && threadIdx.x == 0) g[0] = 0x21212121u;
+  const uint32_t c0 = 16 * threadIdx.x;                            // the unit's first character in the tile
+  const uint32_t n = t.chars - c0 < 16 ? t.chars - c0 : 16;        // its characters (the final unit: 8, 12 or 16)
+  if (n == 16 && c0 + 16 <= t.store && (((uintptr_t)(dst + c0)) & 15) == 0) {
+    st16(dst + c0, make_uint4(g[0], g[1], g[2], g[3]));
+    return;
+  }
+  for (uint32_t k = 0; k < n && c0 + k < t.store; ++k) {
+    const bool pad = c0 + k + t.pad >= t.chars;  // the text's last t.pad characters
+    dst[c0 + k] = pad ? '=' : (char)((g[k >> 2] >> (8 * (k & 3))) & 0xFF);
+  }
+}
+
+__global__ __launch_bounds__(kB64Block) void k_odo_b64_seg(RespondFields f, const uint64_t* __restrict__ woff,
+                                                            const uint64_t* __restrict__ toff, size_t n_objects,
+                                                            uint64_t total_words, uint64_t nchars,
+                                                            const unsigned long long* __restrict__ reject) {
+  __shared__ uint32_t lds[3 * kB64Block];
+  const WireTile wt = wire_tile_find(woff, n_objects, blockIdx.x);
+  const RespondTile t = respond_tile(woff, toff, wt.object, wt.local, total_words, nchars);
+  if (!t.words || !t.store) return;
+  const bool mark = t.first && reject && reject[wt.object] != kNoFail;
+  for (int k = 0; k < 5; ++k) {
+    if (k) __syncthreads();  // the LDS tile of field k - 1 has been read
+    odo_b64_tile(f.in[k], f.out[k], t, mark, lds);
+  }
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 unsigned grid_n(size_t n, const LaunchCfg& c) {
@@ -395,6 +475,21 @@ hipError_t launch_b64_encode_multi(const uint8_t* const* in, char* const* out, i
   const size_t units = (nbytes + 11) / 12;
   AMPH_LAUNCH(k_b64_encode_multi, dim3((unsigned)((units + kB64Block - 1) / kB64Block), (unsigned)n),
               dim3(kB64Block), c, st, nbytes);
+  return hipGetLastError();
+}
+
+hipError_t launch_odo_b64_seg(const uint8_t* const* in, char* const* out, const uint64_t* woff,
+                              const uint64_t* toff, size_t n_objects, size_t grid, uint64_t total_words,
+                              uint64_t nchars, const unsigned long long* reject, const LaunchCfg& c) {
+  if (n_objects == 0 || total_words == 0 || nchars == 0 || grid == 0) return hipSuccess;
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  RespondFields f{};
+  for (int k = 0; k < 5; ++k) {
+    f.in[k] = in[k];
+    f.out[k] = out[k];
+  }
+  AMPH_LAUNCH(k_odo_b64_seg, dim3((unsigned)grid), dim3(kB64Block), c, f, woff, toff, n_objects, total_words, nchars,
+              reject);
   return hipGetLastError();
 }
 

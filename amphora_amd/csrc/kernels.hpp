@@ -154,6 +154,16 @@ hipError_t launch_b64_encode(const uint8_t* in, size_t nbytes, char* out, const 
 // n <= 5 streams of nbytes each, one launch
 hipError_t launch_b64_encode_multi(const uint8_t* const* in, char* const* out, int n, size_t nbytes,
                                    const LaunchCfg& c);
+// Many objects' five ODO fields in one launch (include/amphora_respond_batch.h;
+// respondtiles.hpp): in[k] = field k's packed words (total_words of them, the
+// objects on woff[n_objects + 1]), out[k] = its slotted text buffer of nchars
+// characters (object o's text at toff[o]); all ten 16-byte aligned.  reject:
+// null, or n_objects words -- an object whose word is not kNoFail gets "!!!!"
+// as its texts' first four characters.  grid: wire_tile_grid(T, n_objects)
+// workgroups, or any upper bound of it (surplus workgroups exit).
+hipError_t launch_odo_b64_seg(const uint8_t* const* in, char* const* out, const uint64_t* woff,
+                              const uint64_t* toff, size_t n_objects, size_t grid, uint64_t total_words,
+                              uint64_t nchars, const unsigned long long* reject, const LaunchCfg& c);
 // text_end: the range ends the text, so '=' may pad its last two chars;
 // out_bytes = kB64PadOnDevice (with text_end): the kernel sizes the output
 // from the text's last two characters itself, no host read-back

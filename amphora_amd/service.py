@@ -239,14 +239,9 @@ class OutputDeliveryService:
             data, stride = bytes(share), WORD_WIDTH
         return self._compute(_lib.words_view(data, stride), stride, request_id)
 
-    def _compute(self, share_words, stride, request_id):
-        W = share_words.shape[0]
-        masks = self._download(request_id, INPUT_MASK_GFP, 2 * W)
-        op_id = name_uuid_from_bytes(("%s_%d" % (request_id, 2 * W)).encode())  # :140-141
-        triples = self._download(op_id, MULTIPLICATION_TRIPLE_GFP, 2 * W)
-        if self._session:
-            return self._compute_session(share_words, stride, masks, triples, op_id)
-        y, r, v, mag, neg = self._ctx.odo_pre(share_words, stride, masks, triples)
+    def _open(self, op_id, mag, neg):
+        """The inter-VCP open of one request: this party's diffs out, every
+        party's (own first) back as (mags, negs)."""
         mags, negs = [mag], [neg]
         if self._json:
             from . import wire
@@ -275,6 +270,17 @@ class OutputDeliveryService:
                     negs.append(n)
             except Exception as e:
                 raise AmphoraServiceException("Failed to open values for operation #%s" % op_id) from e
+        return mags, negs
+
+    def _compute(self, share_words, stride, request_id):
+        W = share_words.shape[0]
+        masks = self._download(request_id, INPUT_MASK_GFP, 2 * W)
+        op_id = name_uuid_from_bytes(("%s_%d" % (request_id, 2 * W)).encode())  # :140-141
+        triples = self._download(op_id, MULTIPLICATION_TRIPLE_GFP, 2 * W)
+        if self._session:
+            return self._compute_session(share_words, stride, masks, triples, op_id)
+        y, r, v, mag, neg = self._ctx.odo_pre(share_words, stride, masks, triples)
+        mags, negs = self._open(op_id, mag, neg)
         # recombineDiffs (:231-272) + multiplySharedSecrets (:274-286) + the w/u
         # encoding (:147-152), one launch: the opened values stay on chip
         w, u = self._ctx.open_post(mags, negs, triples, self.player_id == 0)
@@ -311,3 +317,90 @@ class OutputDeliveryService:
         masks = self._download(request_id, INPUT_MASK_GFP, count)
         odo_req = name_uuid_from_bytes(("%s_odo-computation" % request_id).encode())
         return self._compute(masks, 32, odo_req), masks
+
+    # -- K requests at once ------------------------------------------------------------
+    def compute_output_delivery_objects(self, shares, request_ids) -> list:
+        """compute_output_delivery_object for K requests: the tuple downloads
+        and the exchange stay per request (they are the protocol's own), one
+        K_ODO_PRE and one open + K_ODO_POST launch run over the concatenation of
+        the requests' words -- both are word by word, so every request's ODO is
+        bit for bit the single function's.  Returns one entry per request: the
+        OutputDeliveryObject, or the AmphoraServiceException the single function
+        raises for that request (the others are unaffected).
+        exchange_format="session" is one request by construction: a loop."""
+        if len(shares) != len(request_ids):
+            raise ValueError("one request id per share")
+        if self._session:
+            from .client import _outcome
+            return [_outcome(self.compute_output_delivery_object, s, r) for s, r in zip(shares, request_ids)]
+        views = [(_lib.words_view(s.data, SHARE_WIDTH), SHARE_WIDTH) if isinstance(s, SecretShare)
+                 else (_lib.words_view(bytes(s), WORD_WIDTH), WORD_WIDTH) for s in shares]
+        if len({st for _, st in views}) > 1:  # mixed: the value halves alone, which is all K_ODO_PRE reads
+            views = [(np.ascontiguousarray(v[:, :WORD_WIDTH]), WORD_WIDTH) for v, _ in views]
+        return self._compute_many([v for v, _ in views], views[0][1] if views else WORD_WIDTH, request_ids)
+
+    def _compute_many(self, words, stride, request_ids) -> list:
+        K = len(words)
+        out, got = [None] * K, {}
+        for o in range(K):
+            W = words[o].shape[0]
+            try:
+                masks = self._download(request_ids[o], INPUT_MASK_GFP, 2 * W)
+                op_id = name_uuid_from_bytes(("%s_%d" % (request_ids[o], 2 * W)).encode())
+                got[o] = (masks, op_id, self._download(op_id, MULTIPLICATION_TRIPLE_GFP, 2 * W))
+            except AmphoraServiceException as e:
+                out[o] = e
+        live = sorted(got)
+        if not live:
+            return out
+        at, off = 0, {}
+        for o in live:
+            off[o] = at
+            at += words[o].shape[0]
+        y, r, v, mag, neg = self._ctx.odo_pre(np.concatenate([words[o] for o in live]), stride,
+                                              np.concatenate([got[o][0] for o in live]),
+                                              np.concatenate([got[o][2] for o in live]))
+        opened = {}
+        for o in live:  # the exchange works on this request's slice of the packed diffs
+            a, b = 2 * off[o], 2 * (off[o] + words[o].shape[0])
+            try:
+                opened[o] = self._open(got[o][1], mag[a:b], neg[a:b])
+            except AmphoraServiceException as e:
+                out[o] = e
+        groups = {}  # by party count: one open + K_ODO_POST launch each (one group, unless a partner list is off)
+        for o in sorted(opened):
+            groups.setdefault(len(opened[o][0]), []).append(o)
+        for n, members in groups.items():
+            mags = [np.concatenate([opened[o][0][j] for o in members]) for j in range(n)]
+            negs = [np.concatenate([opened[o][1][j] for o in members]) for j in range(n)]
+            w, u = self._ctx.open_post(mags, negs, np.concatenate([got[o][2] for o in members]), self.player_id == 0)
+            g0 = 0
+            for o in members:
+                a, W = off[o], words[o].shape[0]
+                out[o] = OutputDeliveryObject(y[a:a + W].tobytes(), r[a:a + W].tobytes(), v[a:a + W].tobytes(),
+                                              w[g0:g0 + W].tobytes(), u[g0:g0 + W].tobytes())
+                g0 += W
+        return out
+
+    def get_input_masks_as_output_delivery_objects(self, request_ids, counts) -> list:
+        """get_input_masks_as_output_delivery_object for K requests over the
+        stride-32 mask tuples, as compute_output_delivery_objects: one entry per
+        request, (ODO, the mask tuple stream to cache) or the request's
+        AmphoraServiceException."""
+        if len(request_ids) != len(counts):
+            raise ValueError("one count per request id")
+        if self._session:
+            from .client import _outcome
+            return [_outcome(self.get_input_masks_as_output_delivery_object, r, c)
+                    for r, c in zip(request_ids, counts)]
+        out, masks = [None] * len(request_ids), {}
+        for o, (rid, count) in enumerate(zip(request_ids, counts)):
+            try:
+                masks[o] = self._download(rid, INPUT_MASK_GFP, count)
+            except AmphoraServiceException as e:
+                out[o] = e
+        live = sorted(masks)
+        odo_reqs = [name_uuid_from_bytes(("%s_odo-computation" % request_ids[o]).encode()) for o in live]
+        for o, res in zip(live, self._compute_many([masks[o] for o in live], 32, odo_reqs)):
+            out[o] = res if isinstance(res, Exception) else (res, masks[o])
+        return out

@@ -58,7 +58,10 @@ def _pretty_tags(tags, indent="  "):
 def vss_to_json(ctx: _lib.Context, secret_id: uuid.UUID, tags, odo: OutputDeliveryObject,
                 pretty: bool = True) -> str:
     """VerifiableSecretShare -> JSON (Jackson's pretty printer layout when pretty)."""
-    b64 = [ctx.base64_encode(bytes(f)).decode("ascii") for f in odo.fields()]
+    return _vss_json(secret_id, tags, [ctx.base64_encode(bytes(f)).decode("ascii") for f in odo.fields()], pretty)
+
+
+def _vss_json(secret_id, tags, b64, pretty):
     if pretty:
         lines = ['  "secretId" : "%s"' % secret_id, '  "tags" : %s' % _pretty_tags(tags)]
         lines += ['  "%s" : "%s"' % (k, v) for k, v in zip(ODO_FIELDS, b64)]
@@ -71,6 +74,28 @@ def vss_to_json(ctx: _lib.Context, secret_id: uuid.UUID, tags, odo: OutputDelive
 def odo_to_json(ctx: _lib.Context, odo: OutputDeliveryObject) -> str:
     b64 = [ctx.base64_encode(bytes(f)).decode("ascii") for f in odo.fields()]
     return "{" + ",".join('"%s":"%s"' % (k, v) for k, v in zip(ODO_FIELDS, b64)) + "}"
+
+
+def _odo_texts_batch(ctx: _lib.Context, odos) -> List[List[str]]:
+    """The five base64 strings of every ODO, all coded in one launch
+    (amph_odo_fields_b64_batch)."""
+    texts = ctx.odo_fields_b64_batch([[np.frombuffer(bytes(f), np.uint8) for f in odo.fields()] for odo in odos])
+    return [[t.decode("ascii") for t in five] for five in texts]
+
+
+def vss_bodies_to_json(ctx: _lib.Context, secret_ids, tags_list, odos, pretty: bool = True) -> List[str]:
+    """vss_to_json for K responses with one batch call for their 5 K base64
+    fields; entry by entry the text vss_to_json gives."""
+    if not (len(secret_ids) == len(tags_list) == len(odos)):
+        raise ValueError("one secret id and one tag list per OutputDeliveryObject")
+    return [_vss_json(sid, tags, b64, pretty)
+            for sid, tags, b64 in zip(secret_ids, tags_list, _odo_texts_batch(ctx, odos))]
+
+
+def odo_bodies_to_json(ctx: _lib.Context, odos) -> List[str]:
+    """odo_to_json for K responses with one batch call."""
+    return ["{" + ",".join('"%s":"%s"' % (k, v) for k, v in zip(ODO_FIELDS, b64)) + "}"
+            for b64 in _odo_texts_batch(ctx, odos)]
 
 
 _SIGNIFICANT = re.compile(r'["{}\[\]]')

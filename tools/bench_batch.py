@@ -4,6 +4,7 @@ and what batching buys ("Packed calls").
     python tools/bench_batch.py [--reps R] [--out FILE]
     python tools/bench_batch.py --wire [--variant-lib LIB] [--reps R] [--out FILE]
     python tools/bench_batch.py --upload [--reps R] [--out FILE]
+    python tools/bench_batch.py --respond [--reps R] [--out FILE]
 
 GPU only (fails without a device).  Everything is warmed up, then timed in
 alternating order within this one process; one JSON line with the build id.
@@ -45,6 +46,17 @@ include/amphora_upload_batch.h), same method, one run on one board:
 * hot path at ONE object of the same 256,000 words, kernel time: k_mask_json
   (twice per round: the spread) against k_mask_json_seg at 2 and 3 parties,
   k_conv_json (twice) against k_conv_json_seg.
+
+--respond measures the many-responses call (DESIGN.md section 4c''',
+include/amphora_respond_batch.h), same method, one run on one board:
+
+* batching: 256 objects x 1,000 words.  Device: one amph_odo_fields_b64_packed
+  call against 5 x 256 enqueued amph_base64_encode device calls, one
+  synchronise per side.  Host: amph_odo_fields_b64_batch and _packed against
+  5 x 256 host amph_base64_encode calls.
+* hot path at ONE object of the same 256,000 words, kernel time: k_odo_b64_seg
+  against the SUM of the five k_b64_encode_blk launches amph_base64_encode makes
+  for the five fields, that sum taken twice per round (a, a2: the spread).
 """
 import argparse
 import ctypes as C
@@ -71,6 +83,7 @@ ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
 ap.add_argument("--wire", action="store_true", help="the many-secrets wire-text calls (section 4c')")
 ap.add_argument("--upload", action="store_true", help="the many-uploads calls (section 4c'')")
+ap.add_argument("--respond", action="store_true", help="the many-responses call (section 4c''')")
 ap.add_argument("--variant-lib", default=None, help="--wire: a library built with -DAMPH_WIRE_SEG_LANES=0")
 a = ap.parse_args()
 
@@ -549,6 +562,135 @@ def upload_mode():
     result["party"] = {"batching": bat, "hot_path_one_object_of_%d_words" % T: hot}
     emit(result)
 
+
+# ---------------------------------------------------------------- --respond
+def board_identity():
+    """The host and the board's own sysfs identity, as bench.py records them."""
+    import socket
+    p = torch.cuda.get_device_properties(0)
+    bus = "%04x:%02x:%02x.0" % (p.pci_domain_id, p.pci_bus_id, p.pci_device_id)
+    out = {"host": socket.gethostname(), "pci_bus_id": bus}
+    for k in ("unique_id", "serial_number", "vbios_version", "product_name"):
+        try:
+            v = open("/sys/bus/pci/devices/%s/%s" % (bus, k)).read().strip()
+            if v:
+                out[k] = v
+        except OSError:
+            pass
+    return out
+
+
+def respond_mode():
+    F_DEV = _lib.AMPH_F_DEVICE
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    nchars_of, slot_of = _lib.wire_text_chars, _lib.wire_slot_chars
+
+    def ok(st):
+        if st != 0:
+            raise RuntimeError(L.amph_last_error().decode())
+
+    K, WO = 256, 1000
+    T = K * WO
+    sl = slot_of(WO)
+    assert nchars_of(WO) <= sl
+    breps = max(5, a.reps // 2)
+    fields = ctx.synth_words(31, 5 * T).reshape(5, T, 16)
+    hfields = fields.cpu().numpy()
+    result = {"tool": "bench_batch --respond", "build_id": _lib.check_build_id(),
+              "device": torch.cuda.get_device_name(0), "board": board_identity(), "reps": a.reps,
+              "warmup": a.warmup, "objects": K, "words_per_object": WO, "batching_reps": breps,
+              "timing": {"batching": "wall clock, one synchronise per side", "hot_path": "kernel dispatch events"}}
+
+    # ---- batching: K objects' 5 K texts
+    woff = torch.arange(0, T + 1, WO, dtype=torch.int64, device="cuda")
+    toff = torch.arange(0, K * sl, sl, dtype=torch.int64, device="cuda")
+    out_p = torch.zeros((5, K * sl), dtype=torch.uint8, device="cuda")
+    out_s = torch.zeros((5, K * sl), dtype=torch.uint8, device="cuda")
+    odo_d = _lib._AmphOdo(*[fields[k].data_ptr() for k in range(5)], 16 * T)
+    ob_d = _lib._AmphOdoB64Out(*[out_p[k].data_ptr() for k in range(5)], K * sl)
+    hwoff, htoff = woff.cpu().numpy().astype(np.uint64), toff.cpu().numpy().astype(np.uint64)
+    hout_p, hout_s, hout_b = (np.zeros((5, K * sl), np.uint8) for _ in range(3))
+    odo_h = _lib._AmphOdo(*[hfields[k].ctypes.data for k in range(5)], 16 * T)
+    ob_h = _lib._AmphOdoB64Out(*[hout_p[k].ctypes.data for k in range(5)], K * sl)
+    gathered = (_lib._AmphOdo * K)(*[_lib._AmphOdo(*[hfields[k].ctypes.data + 16 * WO * o for k in range(5)], 16 * WO)
+                                     for o in range(K)])
+    pout = (C.c_void_p * (5 * K))(*[hout_b[k].ctypes.data + sl * o for o in range(K) for k in range(5)])
+    dsingles = [(fields[k].data_ptr() + 16 * WO * o, out_s[k].data_ptr() + sl * o) for o in range(K) for k in range(5)]
+    hsingles = [(hfields[k].ctypes.data + 16 * WO * o, hout_s[k].ctypes.data + sl * o)
+                for o in range(K) for k in range(5)]
+
+    def dev_singles():
+        for src, dst in dsingles:
+            ok(L.amph_base64_encode(ctx._h, src, 16 * WO, dst, F_DEV, stream))
+        torch.cuda.synchronize()
+
+    def dev_packed(ob=ob_d, wo=woff, to=toff, k=K):
+        ok(L.amph_odo_fields_b64_packed(ctx._h, C.byref(odo_d), wo.data_ptr(), to.data_ptr(), k, C.byref(ob), None,
+                                        F_DEV, stream))
+
+    def dev_packed_synced():
+        dev_packed()
+        torch.cuda.synchronize()
+
+    def host_singles():
+        for src, dst in hsingles:
+            ok(L.amph_base64_encode(ctx._h, src, 16 * WO, dst, 0, None))
+
+    bat = alternate({
+        "device_1280_base64_encode": dev_singles,
+        "device_odo_fields_b64_packed": dev_packed_synced,
+        "host_1280_base64_encode": host_singles,
+        "host_odo_fields_b64_batch": lambda: ok(L.amph_odo_fields_b64_batch(ctx._h, gathered, K, pout, None, 0)),
+        "host_odo_fields_b64_packed": lambda: ok(L.amph_odo_fields_b64_packed(
+            ctx._h, C.byref(odo_h), hwoff.ctypes.data, htoff.ctypes.data, K, C.byref(ob_h), None, 0, None)),
+    }, breps, 3, wall_ms)
+    assert torch.equal(out_p, out_s) and np.array_equal(hout_p, hout_s) and np.array_equal(hout_b, hout_s)
+    assert np.array_equal(out_p.cpu().numpy(), hout_s)
+    d1, dp = bat["device_1280_base64_encode"], bat["device_odo_fields_b64_packed"]
+    bat["speedup"] = {
+        "device: singles / packed": ratio(bat, "device_1280_base64_encode", "device_odo_fields_b64_packed"),
+        "host: singles / batch": ratio(bat, "host_1280_base64_encode", "host_odo_fields_b64_batch"),
+        "host: singles / packed": ratio(bat, "host_1280_base64_encode", "host_odo_fields_b64_packed"),
+    }
+    bat["device_quartile_ranges_disjoint"] = bool(dp["p75_ms"] < d1["p25_ms"])
+    result["batching"] = bat
+
+    # ---- hot path: ONE object of T words
+    one_chars = slot_of(T)
+    o_seg = torch.zeros((5, one_chars), dtype=torch.uint8, device="cuda")
+    o_blk = torch.zeros((5, one_chars), dtype=torch.uint8, device="cuda")
+    w1 = torch.tensor([0, T], dtype=torch.int64, device="cuda")
+    z1 = torch.zeros(1, dtype=torch.int64, device="cuda")
+    ob_1 = _lib._AmphOdoB64Out(*[o_seg[k].data_ptr() for k in range(5)], one_chars)
+
+    def five_blk_ms():
+        """The five fields' k_b64_encode_blk launches, each timed by its own dispatch events, summed."""
+        return sum(kernel_ms(lambda k=k: ok(L.amph_base64_encode(ctx._h, fields[k].data_ptr(), 16 * T,
+                                                                 o_blk[k].data_ptr(), F_DEV, stream)))
+                   for k in range(5))
+
+    def seg_ms():
+        return kernel_ms(lambda: dev_packed(ob=ob_1, wo=w1, to=z1, k=1))
+
+    hot = alternate({"five_k_b64_encode_blk_a": five_blk_ms, "k_odo_b64_seg_1_object": seg_ms,
+                     "five_k_b64_encode_blk_a2": five_blk_ms}, a.reps, a.warmup, lambda fn: fn())
+    assert torch.equal(o_seg, o_blk)
+    base, seg = hot["five_k_b64_encode_blk_a"]["median_ms"], hot["k_odo_b64_seg_1_object"]["median_ms"]
+    hot["ratios"] = {"five_blk_a2_over_a (spread)": ratio(hot, "five_k_b64_encode_blk_a2", "five_k_b64_encode_blk_a"),
+                     "k_odo_b64_seg_1_object_over_five_blk": ratio(hot, "k_odo_b64_seg_1_object",
+                                                                   "five_k_b64_encode_blk_a")}
+    hot["difference_us"] = {"seg_minus_five_blk": round(1e3 * (seg - base), 3),
+                            "five_blk_a2_minus_a (spread)": round(
+                                1e3 * (hot["five_k_b64_encode_blk_a2"]["median_ms"] - base), 3)}
+    result["hot_path_one_object_of_%d_words" % T] = hot
+
+    emit(result)
+
+
+if a.respond:
+    respond_mode()
+    del ctx  # (destroyed while the library is still loaded)
+    sys.exit(0)
 
 if a.upload:
     upload_mode()
