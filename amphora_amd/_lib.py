@@ -807,29 +807,13 @@ class Context:
         s = words_view(secrets16) if masked else None
         flags, stream = self._mode(s, *keep)
         like = keep[0]
-        wo = np.ascontiguousarray(word_offsets, dtype=np.uint64) if not _is_dev(word_offsets) else word_offsets
-        to = np.ascontiguousarray(text_offsets, dtype=np.uint64) if not _is_dev(text_offsets) else text_offsets
-        K = max(0, (wo.numel() if _is_dev(wo) else wo.size) - 1)
-        if (to.numel() if _is_dev(to) else to.size) != K:
+        K = max(0, len(word_offsets) - 1)
+        if len(text_offsets) != K:
             raise ValueError("one text offset per object, one more word offset")
-        T = int(wo[-1]) if K else 0
-        if flags & AMPH_F_DEVICE:
-            import torch
-            wo, to = [x if _is_dev(x) else torch.as_tensor(x.view(np.int64)).to(like.device) for x in (wo, to)]
-            verdicts = []
-            for v in (first_fail, bad_char):
-                if v is None:
-                    v = torch.empty(K, dtype=torch.int64, device=like.device)
-                    accumulate = False
-                elif v.numel() != K or v.dtype != torch.int64 or not v.is_cuda:
-                    raise ValueError("verdict arrays must be int64 device tensors with one entry per object")
-                verdicts.append(v)
-            first_fail, bad_char = verdicts
-            if accumulate:
-                flags |= AMPH_F_ACCUMULATE
-        else:
-            first_fail = np.full(K, -1, dtype=np.int64)
-            bad_char = np.full(K, -1, dtype=np.int64)
+        T = int(word_offsets[-1]) if K else 0
+        (wo, to), (first_fail, bad_char), acc = self._tables(like, K, (word_offsets, text_offsets),
+                                                             (first_fail, bad_char), accumulate)
+        flags |= acc
         if masked:
             _need(s.shape[0] == T, "the packed form takes one secret per input mask word")
             o16 = self._empty(like, (T, 16)) if raw else None
@@ -843,16 +827,44 @@ class Context:
             st = lib.amph_recombine_verify_b64_packed(self._h, arr, len(texts), _ptr(wo), _ptr(to), K, _ptr(out),
                                                       _ptr(first_fail), _ptr(bad_char), flags, stream)
             res = (out, first_fail, bad_char)
-        return self._wire_batch_result(st, res, bad_char, status)
+        return self._batch_result(st, res, bad_char, status)
 
-    def _wire_batch_result(self, st, res, bad_char, status):
+    def _batch_result(self, st, res, verdict, status):
         """Per-object verdicts are the result: AMPH_E_VERIFY, and AMPH_E_PARAM
-        with a bad character reported, return them (status=True appends
-        (status, amph_last_error)); anything else raises."""
+        with a bad character / offending byte reported in `verdict`, return
+        them (status=True appends (status, amph_last_error)); anything else
+        raises."""
         msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
-        if not (st == AMPH_E_PARAM and not _is_dev(bad_char) and (np.asarray(bad_char) >= 0).any()):
+        if not (st == AMPH_E_PARAM and not _is_dev(verdict) and (np.asarray(verdict) >= 0).any()):
             self._check(st, allow_verify=True)
         return res + ((st, msg),) if status else res
+
+    def _gather_objects(self, objects):
+        """The gathered calls' objects[o][j] (host texts, as _text_structs) as
+        one _AmphOdoB64 array [o * n + j]: (array, n, keep-alive list)."""
+        K = len(objects)
+        n = len(objects[0]) if K else 1
+        arr = (_AmphOdoB64 * max(1, K * n))()
+        keep = []
+        for o, obj in enumerate(objects):
+            if len(obj) != n:
+                raise ValueError("every object needs the same number of parties")
+            a, ks = self._text_structs(obj)
+            if any(_is_dev(f) for f in ks):
+                raise ValueError("the batch calls take host buffers")
+            keep.append(ks)
+            for j in range(n):
+                arr[o * n + j] = a[j]
+        return arr, n, keep
+
+    @staticmethod
+    def _dense_offsets(word_offsets, stride):
+        """The default slots of a packed call's texts: object o's at the sum of
+        its predecessors' stride(W) -- (offsets[K], capacity).  (A decreasing
+        table gets an empty slot here and its refusal from the library.)"""
+        wo = [int(x) for x in (word_offsets.cpu() if _is_dev(word_offsets) else word_offsets)]
+        ends = np.cumsum([stride(max(0, b - a)) for a, b in zip(wo, wo[1:])], dtype=np.uint64)
+        return np.concatenate([[0], ends]).astype(np.uint64)[:len(ends)], int(ends[-1]) if len(ends) else 0
 
     def recombine_verify_b64_packed(self, texts, word_offsets, text_offsets, first_fail=None, bad_char=None,
                                     accumulate=False, status=False):
@@ -876,18 +888,7 @@ class Context:
 
     def _wire_batch(self, masked, objects, words, secrets, records, raw, status):
         K = len(objects)
-        n = len(objects[0]) if K else 1
-        arr = (_AmphOdoB64 * max(1, K * n))()
-        keep = []
-        for o, obj in enumerate(objects):
-            if len(obj) != n:
-                raise ValueError("every object needs the same number of parties")
-            a, ks = self._text_structs(obj)
-            if any(_is_dev(f) for f in ks):
-                raise ValueError("the batch calls take host buffers")
-            keep.append(ks)
-            for j in range(n):
-                arr[o * n + j] = a[j]
+        arr, n, keep = self._gather_objects(objects)
         wd = (C.c_size_t * max(1, K))(*[int(w) for w in words])
         ff = np.full(K, -1, dtype=np.int64)
         bad = np.full(K, -1, dtype=np.int64)
@@ -909,7 +910,7 @@ class Context:
             st = lib.amph_recombine_verify_b64_batch(self._h, arr, n, K, wd, ptrs(outs), ff.ctypes.data_as(i64p),
                                                      bad.ctypes.data_as(i64p), 0)
             res = (outs, ff, bad)
-        return self._wire_batch_result(st, res, bad, status)
+        return self._batch_result(st, res, bad, status)
 
     def recombine_verify_b64_batch(self, objects, words, status=False):
         """objects: list over secrets of recombine_verify_b64's `texts` (host
@@ -943,7 +944,7 @@ class Context:
         return np.ascontiguousarray(x, np.uint8).reshape(-1)
 
     def _tables(self, like, K, tables, verdicts, accumulate):
-        """The offset tables and verdict arrays of a packed upload call where
+        """The offset tables and verdict arrays of a packed batch call where
         `like` lives: (tables, verdicts, extra flags)."""
         if _is_dev(like):
             import torch
@@ -960,13 +961,6 @@ class Context:
             return tables, out, (AMPH_F_ACCUMULATE if accumulate else 0)
         return ([np.ascontiguousarray(x, dtype=np.uint64) for x in tables],
                 [np.full(K, -1, dtype=np.int64) for _ in verdicts], 0)
-
-    def _upload_result(self, st, res, verdict, status):
-        """Per-object verdicts are the result (as _wire_batch_result)."""
-        msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
-        if not (st == AMPH_E_PARAM and not _is_dev(verdict) and (np.asarray(verdict) >= 0).any()):
-            self._check(st, allow_verify=True)
-        return res + ((st, msg),) if status else res
 
     def convert_share_json_packed(self, texts, word_offsets, text_offsets, tuples32, mac_key: int,
                                   use_zero_input_as_data: bool, out=None, bad_index=None, accumulate=False,
@@ -989,7 +983,7 @@ class Context:
         st = lib.amph_convert_share_json_packed(self._h, _ptr(a), n, _ptr(wo), _ptr(to), K, _ptr(t),
                                                 le16(mac_key % self.prime), int(use_zero_input_as_data), _ptr(out),
                                                 _ptr(bad), flags | acc, stream)
-        return self._upload_result(st, (out, bad), bad, status)
+        return self._batch_result(st, (out, bad), bad, status)
 
     def convert_share_json_batch(self, texts, tuples, mac_key: int, use_zero_input_as_data: bool, status=False):
         """amph_convert_share_json_batch: texts[o] (str / bytes) with
@@ -1008,7 +1002,7 @@ class Context:
                                                szs([x.shape[0] for x in tu]), K, ptrs(tu),
                                                le16(mac_key % self.prime), int(use_zero_input_as_data), ptrs(outs),
                                                bad.ctypes.data_as(C.POINTER(C.c_int64)), 0)
-        return self._upload_result(st, (outs, bad), bad, status)
+        return self._batch_result(st, (outs, bad), bad, status)
 
     def mask_input_json_packed(self, texts, word_offsets, text_offsets, secrets16, out_text_offsets=None,
                                out_text=None, first_fail=None, bad_char=None, accumulate=False, status=False):
@@ -1025,13 +1019,9 @@ class Context:
         K = max(0, len(word_offsets) - 1)
         if len(text_offsets) != K:
             raise ValueError("one text offset per object, one more word offset")
+        cap = None
         if out_text_offsets is None:
-            wo_h = np.asarray(word_offsets.cpu() if _is_dev(word_offsets) else word_offsets, dtype=np.uint64)
-            strides = [upload_slot_chars(int(wo_h[o + 1] - wo_h[o])) for o in range(K)]
-            out_text_offsets = np.concatenate([[0], np.cumsum(strides)]).astype(np.uint64)[:K]
-            cap = int(sum(strides))
-        else:
-            cap = None
+            out_text_offsets, cap = self._dense_offsets(word_offsets, upload_slot_chars)
         if out_text is None:
             if cap is None:
                 raise ValueError("out_text_offsets of the caller's need the caller's out_text")
@@ -1041,25 +1031,14 @@ class Context:
                                                     (first_fail, bad_char), accumulate)
         st = lib.amph_mask_input_json_packed(self._h, arr, len(texts), _ptr(wo), _ptr(to), K, _ptr(s),
                                              _ptr(out_text), cap, _ptr(oo), _ptr(ff), _ptr(bad), flags | acc, stream)
-        return self._upload_result(st, (out_text, oo, ff, bad), bad, status)
+        return self._batch_result(st, (out_text, oo, ff, bad), bad, status)
 
     def mask_input_json_batch(self, objects, words, secrets, status=False):
         """amph_mask_input_json_batch: mask_input_json for K secrets at once
         (host strings / bytes): (list of K texts as bytes, first_fail[K],
         bad_char[K])."""
         K = len(objects)
-        n = len(objects[0]) if K else 1
-        arr = (_AmphOdoB64 * max(1, K * n))()
-        keep = []
-        for o, obj in enumerate(objects):
-            if len(obj) != n:
-                raise ValueError("every object needs the same number of parties")
-            a, ks = self._text_structs(obj)
-            if any(_is_dev(f) for f in ks):
-                raise ValueError("the batch calls take host buffers")
-            keep.append(ks)
-            for j in range(n):
-                arr[o * n + j] = a[j]
+        arr, n, keep = self._gather_objects(objects)
         if len(secrets) != K:
             raise ValueError("one secrets array per object")
         sv = [words_view(x) for x in secrets]
@@ -1072,7 +1051,7 @@ class Context:
         ptrs = lambda xs: (C.c_void_p * max(1, K))(*[x.ctypes.data for x in xs])  # noqa: E731
         st = lib.amph_mask_input_json_batch(self._h, arr, n, K, wd, ptrs(sv), ptrs(outs), ff.ctypes.data_as(i64p),
                                             bad.ctypes.data_as(i64p), 0)
-        return self._upload_result(st, ([x.tobytes() for x in outs], ff, bad), bad, status)
+        return self._batch_result(st, ([x.tobytes() for x in outs], ff, bad), bad, status)
 
     # -- many Output Delivery responses per launch (include/amphora_respond_batch.h) --
     def respond_batch_copies(self) -> int:
@@ -1101,14 +1080,9 @@ class Context:
         flags, stream = self._mode(*fs)
         like = fs[0]
         K = max(0, len(word_offsets) - 1)
+        cap = None
         if text_offsets is None:
-            wo_h = [int(x) for x in (word_offsets.cpu() if _is_dev(word_offsets) else word_offsets)]
-            # (a decreasing table gets an empty slot here and its refusal from the library)
-            strides = [wire_slot_chars(max(0, wo_h[o + 1] - wo_h[o])) for o in range(K)]
-            text_offsets = np.concatenate([[0], np.cumsum(strides)]).astype(np.uint64)[:K]
-            cap = int(sum(strides))
-        else:
-            cap = None
+            text_offsets, cap = self._dense_offsets(word_offsets, wire_slot_chars)
         if len(text_offsets) != K:
             raise ValueError("one text offset per object, one more word offset")
         if out is None:
@@ -1120,15 +1094,13 @@ class Context:
         caps = {(b.numel() if _is_dev(b) else b.size) for b in out}
         if len(caps) != 1:
             raise ValueError("the five output buffers must have one length")
+        (wo, to), _, _ = self._tables(like, K, (word_offsets, text_offsets), (), False)
         if _is_dev(like):
             import torch
-            wo, to = [x if _is_dev(x) else torch.as_tensor(np.ascontiguousarray(x, np.uint64).view(np.int64))
-                      .to(like.device) for x in (word_offsets, text_offsets)]
             if reject is not None and not (_is_dev(reject) and reject.dtype == torch.int64 and reject.numel() == K):
                 raise ValueError("reject must be an int64 device tensor with one entry per object")
             rj = reject
         else:
-            wo, to = [np.ascontiguousarray(x, dtype=np.uint64) for x in (word_offsets, text_offsets)]
             rj = None if reject is None else np.ascontiguousarray(reject, dtype=np.int64)
             if rj is not None and rj.size != K:
                 raise ValueError("one reject word per object")

@@ -1,6 +1,8 @@
-// Internals shared by the units of the C ABI (capi_*.hip): the context, the
-// error and device helpers, the word-array pipeline's types and the buffers
-// of one-shot host calls.  Everything here lives in one namespace of hidden
+// Internals shared by the units of the C ABI (capi_*.hip -- capi_ctx,
+// capi_pipeline, capi_words, capi_text, capi_party and capi_batch, the
+// many-objects-per-call families): the context, the error and device
+// helpers, the word-array pipeline's types and the buffers of one-shot host
+// calls.  Everything here lives in one namespace of hidden
 // visibility: the library exports only what include/amphora.h and its
 // extension headers include/amphora_wire_batch.h,
 // include/amphora_upload_batch.h and include/amphora_respond_batch.h declare.
@@ -175,6 +177,9 @@ hipError_t dev_ensure(amph_ctx* c, DevBuf& b, size_t bytes);
 u128 mulmod_host(const amph_ctx* c, u128 a, u128 b);  // a < p
 amph::LaunchCfg cfg(amph_ctx* c, hipStream_t s, size_t words);
 inline int check_ctx(amph_ctx* c) { return c ? AMPH_OK : fail(AMPH_E_PARAM, "null context"); }
+// where a multi-device context runs the calls that are not sharded: its first device's context
+inline amph_ctx* first_device(amph_ctx* c) { return c->sub.empty() ? c : c->sub[0]; }
+inline const amph_ctx* first_device(const amph_ctx* c) { return c->sub.empty() ? c : c->sub[0]; }
 
 // ---- word-array calls (capi_pipeline.hip) --------------------------------------
 // A word-array call is described by its input and output arrays, each with a
@@ -344,5 +349,11 @@ struct Stager {
 // the verdict word of an exchange decode (`pairs` FactorPairs expected in
 // `len` characters) as the call's status and message (capi_text.hip)
 int decode_status(int64_t bad, size_t len, size_t pairs, int64_t* bad_index);
+
+// ---- the base64 wire texts (capi_text.hip; the batch calls of capi_batch.hip) ----
+extern const char* const kOdoFieldNames[5];
+const char* b64_field(const amph_odo_b64& o, int k);  // field k's text, in ODO order
+// 1..16 parties and their array: what every wire-text call checks first
+int check_parties(const amph_odo_b64* odos, int n);
 
 }  // namespace capi

@@ -236,7 +236,7 @@ int amph_party_begin(amph_ctx* c, const uint8_t* share_data, size_t share_stride
                      const uint8_t* triples, size_t words, int n_parties, uint8_t* oy, uint8_t* orr,
                      uint8_t* ov, amph_party** out) {
   if (int st = party_args(c, share_stride, n_parties, words, share_data, masks, triples, out)) return st;
-  if (!c->sub.empty()) c = c->sub[0];  // a multi-device context runs sessions on its first device
+  c = first_device(c);  // a multi-device context runs sessions on its first device
   HIP_TRY(use_device(c->device));
   std::lock_guard<std::mutex> g(c->mu);
   std::unique_ptr<amph_party> p(new amph_party);

@@ -1,9 +1,8 @@
 // C ABI of libamphora_hip (declared in include/amphora.h): the text forms --
-// base64, the Beaver open exchange codec, K_RV / K_MASK from the wire texts
-// and K_CONV from the MaskedInput "data" array text.
+// base64, the Beaver open exchange codec, K_RV / K_MASK from one object's wire
+// texts and K_CONV from one MaskedInput "data" array text.  The many-objects
+// forms of the last three are capi_batch.hip.
 #include "capi_internal.hpp"
-#include "wiretiles.hpp"
-#include "respondtiles.hpp"
 
 // ---- base64 wire codec ---------------------------------------------------------
 namespace {
@@ -166,6 +165,24 @@ int decode_status(int64_t bad, size_t len, size_t pairs, int64_t* bad_index) {
     return fail(AMPH_E_LEN, "interimValues must hold exactly " + std::to_string(pairs) + " FactorPairs");
   return fail(AMPH_E_PARAM, "Malformed FactorPair JSON at offset " + std::to_string(bad));
 }
+
+const char* const kOdoFieldNames[5] = {"secretShares", "rShares", "vShares", "wShares", "uShares"};
+
+const char* b64_field(const amph_odo_b64& o, int k) {
+  switch (k) {
+    case 0: return o.secret_shares;
+    case 1: return o.r_shares;
+    case 2: return o.v_shares;
+    case 3: return o.w_shares;
+    default: return o.u_shares;
+  }
+}
+
+int check_parties(const amph_odo_b64* odos, int n) {
+  if (!odos || n < 1 || n > AMPH_MAX_PARTIES)
+    return fail(AMPH_E_PARAM, "n_parties must be in [1, 16] with a non-null ODO array");
+  return AMPH_OK;
+}
 }  // namespace capi
 
 extern "C" {
@@ -292,22 +309,9 @@ int amph_exchange_decode(amph_ctx* c, const char* text, size_t len, size_t npair
 
 // ---- K_RV / K_MASK from the wire ----------------------------------------------
 namespace {
-const char* const kOdoFieldNames[5] = {"secretShares", "rShares", "vShares", "wShares", "uShares"};
-
-const char* b64_field(const amph_odo_b64& o, int k) {
-  switch (k) {
-    case 0: return o.secret_shares;
-    case 1: return o.r_shares;
-    case 2: return o.v_shares;
-    case 3: return o.w_shares;
-    default: return o.u_shares;
-  }
-}
-
 // Shared checks; *nchars / *pad for `words` 16-byte words.
 int wire_check(const amph_odo_b64* odos, int n, size_t words, size_t* nchars, uint32_t* pad) {
-  if (!odos || n < 1 || n > AMPH_MAX_PARTIES)
-    return fail(AMPH_E_PARAM, "n_parties must be in [1, 16] with a non-null ODO array");
+  if (int st = check_parties(odos, n)) return st;
   const size_t nb = 16 * words;
   *nchars = 4 * ((nb + 2) / 3);
   *pad = (uint32_t)((3 - nb % 3) % 3);
@@ -566,778 +570,6 @@ int amph_convert_share_json(amph_ctx* c, const char* text, size_t len, size_t wo
     return fail(AMPH_E_PARAM, "Malformed MaskedInput data text at offset " + std::to_string(bad) + " (" + where + ")");
   }
   return h.fetch({{out, dout, 32 * words}});
-}
-
-}  // extern "C"
-
-// ---- K_RV / K_MASK from the wire, many objects per call -------------------------
-// include/amphora_wire_batch.h: the slotted text layout (wire.hip,
-// wiretiles.hpp).  Host mode moves ONE page-locked image to the device and one
-// back, whatever the object count: [word table | text table | 5 n field
-// buffers | secrets] in, [16-byte words | records | 2 K verdict words] out.
-// A call that fits the small-call arena builds the image there and the
-// kernel reads and writes it in place; its verdict arrays stay in device
-// memory (atomics) and come to the arena by launch_take_array before the
-// call's one synchronisation, as run_packed_small.
-namespace {
-int wire_batch_parties(const amph_odo_b64* odos, int n) {
-  if (!odos || n < 1 || n > AMPH_MAX_PARTIES)
-    return fail(AMPH_E_PARAM, "n_parties must be in [1, 16] with a non-null ODO array");
-  return AMPH_OK;
-}
-
-// the host tables of a packed call against the buffers' length
-int check_wire_tables(const uint64_t* woff, const uint64_t* toff, size_t K, size_t nchars) {
-  if (woff[0] != 0) return fail(AMPH_E_PARAM, "word_offsets[0] must be 0");
-  for (size_t o = 0; o < K; ++o)
-    if (woff[o + 1] < woff[o])
-      return fail(AMPH_E_PARAM, "word_offsets must not decrease (entry " + std::to_string(o + 1) + ")");
-  for (size_t o = 0; o < K; ++o) {
-    const uint64_t end = toff[o] + amph::wire_text_chars(woff[o + 1] - woff[o]);
-    if (toff[o] % 16)
-      return fail(AMPH_E_PARAM, "text_offsets[" + std::to_string(o) + "] = " + std::to_string(toff[o]) +
-                                    " must be a multiple of 16");
-    if (end < toff[o] || end > (o + 1 < K ? toff[o + 1] : (uint64_t)nchars))
-      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": its text [" + std::to_string(toff[o]) + ", " +
-                                    std::to_string(end) + ") runs past " +
-                                    (o + 1 < K ? "the next slot at " + std::to_string(toff[o + 1])
-                                               : "the buffers' " + std::to_string(nchars) + " characters"));
-  }
-  return AMPH_OK;
-}
-
-// The verdict words (first-fail array, then bad-character array) as the
-// caller's entries and the call's status.
-int wire_batch_status(const unsigned long long* v, size_t K, const uint64_t* woff, int64_t* first_fail,
-                      int64_t* bad_char) {
-  size_t nbad = 0, nfail = 0, fb = 0, ff = 0;
-  for (size_t o = 0; o < K; ++o) {
-    const bool bad = v[K + o] != amph::kNoFail, failed = !bad && v[o] != amph::kNoFail;
-    if (bad && !nbad++) fb = o;
-    if (failed && !nfail++) ff = o;
-    bad_char[o] = bad ? (int64_t)v[K + o] : -1;
-    first_fail[o] = failed ? (int64_t)v[o] : -1;
-  }
-  if (nbad) {
-    const size_t nc = amph::wire_text_chars(woff[fb + 1] - woff[fb]), f = (size_t)v[K + fb] / nc;
-    return fail(AMPH_E_PARAM, "object " + std::to_string(fb) + ": Illegal base64 character at index " +
-                                  std::to_string((size_t)v[K + fb] % nc) + " of party " + std::to_string(f / 5) +
-                                  "'s " + kOdoFieldNames[f % 5] + " (" + std::to_string(nbad) + " of " +
-                                  std::to_string(K) + " objects hold an illegal character)");
-  }
-  if (nfail)
-    return fail(AMPH_E_VERIFY, "Verification of secret has failed: object " + std::to_string(ff) + " at word " +
-                                   std::to_string(v[ff]) + " (" + std::to_string(nfail) + " of " +
-                                   std::to_string(K) + " objects failed)");
-  return AMPH_OK;
-}
-
-// How a host call's pieces enter and leave the image: text(j, k, o) = party
-// j's field k of object o (nchars_o characters), secrets(o) / out16(o) /
-// out24(o) = object o's words (null: not wanted), out_text(o) = object o's
-// framed "data" array text (amphora_upload_batch.h).
-struct WirePieces {
-  std::function<const char*(int, int, size_t)> text;
-  std::function<const uint8_t*(size_t)> secrets;
-  std::function<uint8_t*(size_t)> out16;
-  std::function<char*(size_t)> out24;
-  std::function<char*(size_t)> out_text;
-};
-
-// Host mode of all four calls, tables validated: woff[K + 1], toff[K] (a
-// field buffer of the image holds `chars` characters).  framed (the mask
-// calls of amphora_upload_batch.h): the output is every object's framed text
-// instead, in the image's own dense 16-byte-aligned slots; the copies count
-// into upload_copies.
-int wire_batch_host(amph_ctx* c, int n, size_t K, const uint64_t* woff, const uint64_t* toff, size_t chars,
-                    bool masked, bool want16, bool want24, const WirePieces& io, int64_t* first_fail,
-                    int64_t* bad_char, bool framed = false) {
-  const size_t T = woff[K];
-  for (size_t o = 0; o < K; ++o) first_fail[o] = bad_char[o] = -1;
-  if (T == 0) {
-    for (size_t o = 0; framed && o < K; ++o) std::memcpy(io.out_text(o), "[]", 2);
-    return AMPH_OK;
-  }
-  if (!c->sub.empty()) c = c->sub[0];
-  std::atomic<uint64_t>& copies = framed ? c->upload_copies : c->wire_copies;
-  const char* kernel = framed ? "k_mask_json_seg" : masked ? "k_mask_b64_seg" : "k_rv_b64_seg";
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(use_device(c->device));
-  hipStream_t s;
-  if (int st = host_stream(c, 0, &s)) return st;
-  const size_t fchars = align256(chars ? chars : 16);
-  const size_t tab_w = 0, tab_t = tab_w + align256(8 * (K + 1)), tab_o = tab_t + align256(8 * K);
-  const size_t txt = tab_o + (framed ? align256(8 * K) : 0);
-  const size_t sec = txt + 5 * (size_t)n * fchars, in_bytes = sec + (masked ? align256(16 * T) : 0);
-  const size_t o16 = in_bytes, o24 = o16 + (want16 ? align256(16 * T) : 0);
-  const size_t otx = o24 + (want24 ? align256(24 * T) : 0);
-  size_t ochars = 0;  // the framed texts' slots: object o's at the sum of its predecessors' strides
-  for (size_t o = 0; framed && o < K; ++o) ochars += amph::upload_slot_chars(woff[o + 1] - woff[o]);
-  const size_t verd = otx + align256(ochars), total = verd + align256(16 * K);
-  const bool small = small_call(c, total);
-  uint8_t *himg, *dimg;
-  unsigned long long* dverd;
-  if (small) {
-    if (c->small.ensure(total + 256) != hipSuccess) return fail(AMPH_E_NOMEM, "small-call arena");
-    if (dev_ensure(c, c->seg, 16 * K) != hipSuccess) return fail(AMPH_E_NOMEM, "verdict arrays");
-    himg = dimg = (uint8_t*)c->small.p;
-    dverd = (unsigned long long*)c->seg.p;
-  } else {
-    if (c->wire_img.ensure(total) != hipSuccess) return fail(AMPH_E_NOMEM, "wire batch image");
-    if (dev_ensure(c, c->wire, total) != hipSuccess) return fail(AMPH_E_NOMEM, "wire staging");
-    himg = (uint8_t*)c->wire_img.p;
-    dimg = (uint8_t*)c->wire.p;
-    dverd = (unsigned long long*)(dimg + verd);
-  }
-  std::memcpy(himg + tab_w, woff, 8 * (K + 1));
-  std::memcpy(himg + tab_t, toff, 8 * K);
-  uint64_t* ooff = (uint64_t*)(himg + tab_o);
-  for (size_t o = 0, at = 0; framed && o < K; ++o) {
-    ooff[o] = at;
-    at += amph::upload_slot_chars(woff[o + 1] - woff[o]);
-  }
-  amph::TextSet tx{};
-  for (int j = 0; j < n; ++j)
-    for (int k = 0; k < 5; ++k) {
-      const size_t at = txt + (size_t)(5 * j + k) * fchars;
-      for (size_t o = 0; o < K; ++o)
-        if (const size_t nc = amph::wire_text_chars(woff[o + 1] - woff[o]))
-          std::memcpy(himg + at + toff[o], io.text(j, k, o), nc);
-      tx.t[k][j] = (const char*)(dimg + at);
-    }
-  for (size_t o = 0; masked && o < K; ++o)
-    if (woff[o + 1] > woff[o]) std::memcpy(himg + sec + 16 * woff[o], io.secrets(o), 16 * (woff[o + 1] - woff[o]));
-  if (!small) {  // page-locked image, idle stream: one blocking copy (kPageableRule)
-    HIP_TRY(hipMemcpy(dimg, himg, in_bytes, hipMemcpyHostToDevice));
-    copies.fetch_add(1, std::memory_order_relaxed);
-  }
-  HIP_TRY(hipMemsetAsync(dverd, 0x7F, 16 * K, s));
-  const uint64_t *dw = (const uint64_t*)(dimg + tab_w), *dt = (const uint64_t*)(dimg + tab_t);
-  const size_t grid = amph::wire_tile_grid(T, K);
-  hipError_t e = framed ? amph::launch_mask_json_seg(tx, n, dw, dt, (const uint64_t*)(dimg + tab_o), K, grid,
-                                                     (const uint4*)(dimg + sec), (char*)(dimg + otx), dverd,
-                                                     dverd + K, c->f, cfg(c, s, T))
-                 : masked ? amph::launch_mask_b64_seg(tx, n, dw, dt, K, grid, (const uint4*)(dimg + sec),
-                                                    want16 ? (uint4*)(dimg + o16) : nullptr,
-                                                    want24 ? (char*)(dimg + o24) : nullptr, dverd, dverd + K, c->f,
-                                                    cfg(c, s, T))
-                        : amph::launch_rv_b64_seg(tx, n, dw, dt, K, grid, (uint4*)(dimg + o16), dverd, dverd + K,
-                                                  c->f, cfg(c, s, T));
-  if (e == hipSuccess && small) e = amph::launch_take_array(dverd, (unsigned long long*)(himg + verd), 2 * K, s);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    return hip_fail(e, kernel);
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  if (!small) {
-    HIP_TRY(hipMemcpy(himg + in_bytes, dimg + in_bytes, total - in_bytes, hipMemcpyDeviceToHost));
-    copies.fetch_add(1, std::memory_order_relaxed);
-  }
-  for (size_t o = 0; o < K; ++o) {
-    const size_t w0 = woff[o], w = woff[o + 1] - w0;
-    if (framed) std::memcpy(io.out_text(o), himg + otx + ooff[o], amph::masked_input_data_chars(w));
-    if (!w) continue;
-    if (want16) std::memcpy(io.out16(o), himg + o16 + 16 * w0, 16 * w);
-    if (want24) std::memcpy(io.out24(o), himg + o24 + 24 * w0, 24 * w);
-  }
-  return wire_batch_status((const unsigned long long*)(himg + verd), K, woff, first_fail, bad_char);
-}
-
-// Both packed calls: `masked` = false runs K_RV (out16 = the secrets out).
-int wire_packed_call(amph_ctx* c, const amph_odo_b64* odos, int n, const uint64_t* woff, const uint64_t* toff,
-                     size_t K, bool masked, const uint8_t* secrets, uint8_t* out16, char* out24,
-                     int64_t* first_fail, int64_t* bad_char, uint32_t flags, void* stream) {
-  if (check_ctx(c)) return AMPH_E_PARAM;
-  AMPH_NO_HOST_IO(flags);
-  if (K == 0) return AMPH_OK;
-  if (int st = wire_batch_parties(odos, n)) return st;
-  if (!woff || !toff || !first_fail || !bad_char)
-    return fail(AMPH_E_PARAM, "null offsets table or verdict array");
-  for (int j = 1; j < n; ++j)
-    if (odos[j].nchars != odos[0].nchars)
-      return fail(AMPH_E_LEN, "party " + std::to_string(j) + ": field buffers of " + std::to_string(odos[j].nchars) +
-                                  " characters, party 0's hold " + std::to_string(odos[0].nchars));
-  const size_t nchars = odos[0].nchars;
-  if (flags & AMPH_F_DEVICE) {
-    amph::TextSet tx{};
-    for (int j = 0; j < n; ++j)
-      for (int k = 0; k < 5; ++k) {
-        tx.t[k][j] = b64_field(odos[j], k);
-        if (nchars && !tx.t[k][j]) return fail(AMPH_E_PARAM, "null ODO field text");
-        if (int st = check_dev_words({tx.t[k][j]})) return st;
-      }
-    if (int st = check_dev_words({secrets, out16, out24})) return st;
-    if (((uintptr_t)woff | (uintptr_t)toff | (uintptr_t)first_fail | (uintptr_t)bad_char) & 7)
-      return fail(AMPH_E_PARAM, "device offset tables and verdict arrays must be 8-byte aligned");
-    if (nchars && ((!masked && !out16) || (masked && !secrets))) return fail(AMPH_E_PARAM, "null secrets/output");
-    if (!c->sub.empty()) c = c->sub[0];
-    HIP_TRY(use_device(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (!(flags & AMPH_F_ACCUMULATE)) {
-      HIP_TRY(hipMemsetAsync(first_fail, 0x7F, 8 * K, s));
-      HIP_TRY(hipMemsetAsync(bad_char, 0x7F, 8 * K, s));
-    }
-    // the word table is the device's: every text of W words takes at least
-    // 64 W / 3 characters of the buffers, so T <= 3 nchars / 64 bounds the
-    // grid (the surplus workgroups find no tile and exit)
-    const size_t tbound = 3 * (nchars / 64) + 3, grid = amph::wire_tile_grid(tbound, K);
-    if (nchars == 0) return AMPH_OK;
-    hipError_t e = masked ? amph::launch_mask_b64_seg(tx, n, woff, toff, K, grid, (const uint4*)secrets,
-                                                      (uint4*)out16, out24, (unsigned long long*)first_fail,
-                                                      (unsigned long long*)bad_char, c->f, cfg(c, s, tbound))
-                          : amph::launch_rv_b64_seg(tx, n, woff, toff, K, grid, (uint4*)out16,
-                                                    (unsigned long long*)first_fail,
-                                                    (unsigned long long*)bad_char, c->f, cfg(c, s, tbound));
-    return e == hipSuccess ? AMPH_OK : hip_fail(e, masked ? "k_mask_b64_seg" : "k_rv_b64_seg");
-  }
-  if (int st = check_wire_tables(woff, toff, K, nchars)) return st;
-  const size_t T = woff[K];
-  if (T) {
-    for (int j = 0; j < n; ++j)
-      for (int k = 0; k < 5; ++k)
-        if (!b64_field(odos[j], k)) return fail(AMPH_E_PARAM, "null ODO field text");
-    if ((!masked && !out16) || (masked && !secrets)) return fail(AMPH_E_PARAM, "null secrets/output");
-  }
-  WirePieces io;
-  io.text = [&](int j, int k, size_t o) { return b64_field(odos[j], k) + toff[o]; };
-  io.secrets = [&](size_t o) { return secrets + 16 * woff[o]; };
-  io.out16 = [&](size_t o) { return out16 + 16 * woff[o]; };
-  io.out24 = [&](size_t o) { return out24 + 24 * woff[o]; };
-  const size_t used = toff[K - 1] + amph::wire_text_chars(woff[K] - woff[K - 1]);  // the last text's end
-  return wire_batch_host(c, n, K, woff, toff, used, masked, out16 != nullptr, out24 != nullptr, io, first_fail,
-                         bad_char);
-}
-
-// The gathered calls: odos[o * n + j], one words[o] per object.  out_texts
-// (amph_mask_input_json_batch): the framed texts instead of out16 / out24.
-int wire_batch_call(amph_ctx* c, const amph_odo_b64* odos, int n, size_t K, const size_t* words, bool masked,
-                    const uint8_t* const* secrets, uint8_t* const* out16, char* const* out24,
-                    int64_t* first_fail, int64_t* bad_char, uint32_t flags, char* const* out_texts = nullptr) {
-  if (check_ctx(c)) return AMPH_E_PARAM;
-  if (flags) return fail(AMPH_E_PARAM, "the gathered batch calls take host memory only (flags must be 0)");
-  if (K == 0) return AMPH_OK;
-  if (int st = wire_batch_parties(odos, n)) return st;
-  if (!words || !first_fail || !bad_char || (!masked && !out16) || (masked && !secrets))
-    return fail(AMPH_E_PARAM, "null pointer array or verdict array");
-  const bool framed = out_texts != nullptr;
-  std::vector<uint64_t> woff(K + 1, 0), toff(K, 0);
-  size_t chars = 0;
-  for (size_t o = 0; o < K; ++o) {
-    const size_t nc = amph::wire_text_chars(words[o]);
-    for (int j = 0; j < n; ++j) {
-      const amph_odo_b64& t = odos[o * (size_t)n + j];
-      if (t.nchars != nc)
-        return fail(AMPH_E_LEN, "object " + std::to_string(o) + ", party " + std::to_string(j) +
-                                    ": base64 fields of " + std::to_string(t.nchars) + " characters, expected " +
-                                    std::to_string(nc) + " for " + std::to_string(words[o]) + " words");
-      for (int k = 0; k < 5 && words[o]; ++k)
-        if (!b64_field(t, k)) return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null ODO field text");
-    }
-    if ((framed && !out_texts[o]) ||
-        (words[o] && ((out16 && !out16[o]) || (out24 && !out24[o]) || (masked && !secrets[o]))))
-      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null secrets/output");
-    woff[o + 1] = woff[o] + words[o];
-    toff[o] = chars;
-    chars += amph::wire_slot_chars(words[o]);
-  }
-  WirePieces io;
-  io.text = [&](int j, int k, size_t o) { return b64_field(odos[o * (size_t)n + j], k); };
-  io.secrets = [&](size_t o) { return secrets[o]; };
-  io.out16 = [&](size_t o) { return out16[o]; };
-  io.out24 = [&](size_t o) { return out24[o]; };
-  io.out_text = [&](size_t o) { return out_texts[o]; };
-  return wire_batch_host(c, n, K, woff.data(), toff.data(), chars, masked, out16 != nullptr, out24 != nullptr, io,
-                         first_fail, bad_char, framed);
-}
-}  // namespace
-
-extern "C" {
-
-size_t amph_wire_slot_chars(size_t words) { return amph::wire_slot_chars(words); }
-
-uint64_t amph_wire_batch_copies(const amph_ctx* c) {
-  if (!c) return 0;
-  return (c->sub.empty() ? c : c->sub[0])->wire_copies.load(std::memory_order_relaxed);
-}
-
-int amph_recombine_verify_b64_packed(amph_ctx* c, const amph_odo_b64* odos, int n, const uint64_t* word_offsets,
-                                     const uint64_t* text_offsets, size_t n_objects, uint8_t* out_secrets,
-                                     int64_t* first_fail, int64_t* bad_char, uint32_t flags, void* stream) {
-  return wire_packed_call(c, odos, n, word_offsets, text_offsets, n_objects, false, nullptr, out_secrets, nullptr,
-                          first_fail, bad_char, flags, stream);
-}
-
-int amph_mask_input_b64_packed(amph_ctx* c, const amph_odo_b64* odos, int n, const uint64_t* word_offsets,
-                               const uint64_t* text_offsets, size_t n_objects, const uint8_t* secrets,
-                               uint8_t* out_masked16, char* out_records24, int64_t* first_fail, int64_t* bad_char,
-                               uint32_t flags, void* stream) {
-  return wire_packed_call(c, odos, n, word_offsets, text_offsets, n_objects, true, secrets, out_masked16,
-                          out_records24, first_fail, bad_char, flags, stream);
-}
-
-int amph_recombine_verify_b64_batch(amph_ctx* c, const amph_odo_b64* odos, int n, size_t n_objects,
-                                    const size_t* words, uint8_t* const* out_secrets, int64_t* first_fail,
-                                    int64_t* bad_char, uint32_t flags) {
-  return wire_batch_call(c, odos, n, n_objects, words, false, nullptr, out_secrets, nullptr, first_fail, bad_char,
-                         flags);
-}
-
-int amph_mask_input_b64_batch(amph_ctx* c, const amph_odo_b64* odos, int n, size_t n_objects, const size_t* words,
-                              const uint8_t* const* secrets, uint8_t* const* out_masked16,
-                              char* const* out_records24, int64_t* first_fail, int64_t* bad_char, uint32_t flags) {
-  return wire_batch_call(c, odos, n, n_objects, words, true, secrets, out_masked16, out_records24, first_fail,
-                         bad_char, flags);
-}
-
-}  // extern "C"
-
-// ---- many MaskedInput uploads per call (include/amphora_upload_batch.h) ---------
-// Party side: K "data" array texts through k_conv_json_seg.  Host mode as the
-// wire batch calls': ONE page-locked image in -- [word table | text table |
-// texts | tuples] -- and one back -- [shares | K verdict words]; a call that
-// fits the small-call arena is built there, with its verdict words in device
-// memory (atomics) until launch_take_array brings them over.
-// Client side: wire_batch_host's framed form (k_mask_json_seg).
-namespace {
-struct UploadPieces {  // object o's text, tuples and share rows
-  std::function<const char*(size_t)> text;
-  std::function<const uint8_t*(size_t)> tuples;
-  std::function<uint8_t*(size_t)> out;
-};
-
-// woff validated; itoff[o] = where object o's text goes in the image's text
-// region of `chars` bytes
-int upload_conv_host(amph_ctx* c, size_t K, const uint64_t* woff, const std::vector<uint64_t>& itoff, size_t chars,
-                     const UploadPieces& io, const W4& alpha, int use_zero, int64_t* bad_index) {
-  const size_t T = woff[K];
-  for (size_t o = 0; o < K; ++o) bad_index[o] = -1;
-  if (!c->sub.empty()) c = c->sub[0];
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(use_device(c->device));
-  hipStream_t s;
-  if (int st = host_stream(c, 0, &s)) return st;
-  const size_t tab_w = 0, tab_t = tab_w + align256(8 * (K + 1)), txt = tab_t + align256(8 * K);
-  const size_t tup = txt + align256(chars + 16), in_bytes = tup + align256(32 * T + 16);
-  const size_t osh = in_bytes, verd = osh + align256(32 * T + 16), total = verd + align256(8 * K);
-  const bool small = small_call(c, total);
-  uint8_t *himg, *dimg;
-  unsigned long long* dverd;
-  if (small) {
-    if (c->small.ensure(total + 256) != hipSuccess) return fail(AMPH_E_NOMEM, "small-call arena");
-    if (dev_ensure(c, c->seg, 8 * K) != hipSuccess) return fail(AMPH_E_NOMEM, "verdict array");
-    himg = dimg = (uint8_t*)c->small.p;
-    dverd = (unsigned long long*)c->seg.p;
-  } else {
-    if (c->wire_img.ensure(total) != hipSuccess) return fail(AMPH_E_NOMEM, "upload batch image");
-    if (dev_ensure(c, c->wire, total) != hipSuccess) return fail(AMPH_E_NOMEM, "upload staging");
-    himg = (uint8_t*)c->wire_img.p;
-    dimg = (uint8_t*)c->wire.p;
-    dverd = (unsigned long long*)(dimg + verd);
-  }
-  std::memcpy(himg + tab_w, woff, 8 * (K + 1));
-  std::memcpy(himg + tab_t, itoff.data(), 8 * K);
-  for (size_t o = 0; o < K; ++o) {
-    const size_t w = woff[o + 1] - woff[o];
-    std::memcpy(himg + txt + itoff[o], io.text(o), amph::masked_input_data_chars(w));
-    if (w) std::memcpy(himg + tup + 32 * woff[o], io.tuples(o), 32 * w);
-  }
-  if (!small) {  // page-locked image, idle stream: one blocking copy (kPageableRule)
-    HIP_TRY(hipMemcpy(dimg, himg, in_bytes, hipMemcpyHostToDevice));
-    c->upload_copies.fetch_add(1, std::memory_order_relaxed);
-  }
-  HIP_TRY(hipMemsetAsync(dverd, 0x7F, 8 * K, s));
-  hipError_t e = amph::launch_convert_share_json_seg(
-      (const char*)(dimg + txt), (const uint64_t*)(dimg + tab_w), (const uint64_t*)(dimg + tab_t), K,
-      amph::wire_tile_grid(T, K, amph::kConvTileWords), (const uint4*)(dimg + tup), alpha, use_zero,
-      (uint4*)(dimg + osh), dverd, c->f, cfg(c, s, T));
-  if (e == hipSuccess && small) e = amph::launch_take_array(dverd, (unsigned long long*)(himg + verd), K, s);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    return hip_fail(e, "k_conv_json_seg");
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  if (!small) {
-    HIP_TRY(hipMemcpy(himg + in_bytes, dimg + in_bytes, total - in_bytes, hipMemcpyDeviceToHost));
-    c->upload_copies.fetch_add(1, std::memory_order_relaxed);
-  }
-  const unsigned long long* v = (const unsigned long long*)(himg + verd);
-  size_t nbad = 0, fb = 0;
-  for (size_t o = 0; o < K; ++o) {
-    const size_t w = woff[o + 1] - woff[o];
-    if (v[o] != amph::kNoFail) {
-      bad_index[o] = (int64_t)v[o];
-      if (!nbad++) fb = o;
-    }
-    if (w) std::memcpy(io.out(o), himg + osh + 32 * woff[o], 32 * w);
-  }
-  if (nbad) {
-    const int64_t bad = bad_index[fb];
-    const std::string where = bad == 0 ? "the leading '['" : "record " + std::to_string((bad - 1) / 37);
-    return fail(AMPH_E_PARAM, "object " + std::to_string(fb) + ": Malformed MaskedInput data text at offset " +
-                                  std::to_string(bad) + " (" + where + "; " + std::to_string(nbad) + " of " +
-                                  std::to_string(K) + " texts refused)");
-  }
-  return AMPH_OK;
-}
-
-int check_word_table(const uint64_t* woff, size_t K) {
-  if (woff[0] != 0) return fail(AMPH_E_PARAM, "word_offsets[0] must be 0");
-  for (size_t o = 0; o < K; ++o)
-    if (woff[o + 1] < woff[o])
-      return fail(AMPH_E_PARAM, "word_offsets must not decrease (entry " + std::to_string(o + 1) + ")");
-  return AMPH_OK;
-}
-}  // namespace
-
-extern "C" {
-
-size_t amph_upload_slot_chars(size_t words) { return amph::upload_slot_chars(words); }
-
-uint64_t amph_upload_batch_copies(const amph_ctx* c) {
-  if (!c) return 0;
-  return (c->sub.empty() ? c : c->sub[0])->upload_copies.load(std::memory_order_relaxed);
-}
-
-int amph_convert_share_json_packed(amph_ctx* c, const char* texts, size_t texts_len, const uint64_t* woff,
-                                   const uint64_t* toff, size_t K, const uint8_t* tuples,
-                                   const uint8_t mac_key_le[16], int use_zero, uint8_t* out, int64_t* bad_index,
-                                   uint32_t flags, void* stream) {
-  if (check_ctx(c)) return AMPH_E_PARAM;
-  AMPH_NO_HOST_IO(flags);
-  if (K == 0) return AMPH_OK;
-  if (!mac_key_le) return fail(AMPH_E_PARAM, "null mac key");
-  if (!texts || !woff || !toff || !bad_index) return fail(AMPH_E_PARAM, "null text, offsets table or verdict array");
-  const W4 alpha = amph::mont_mul(w4_of(ld128(mac_key_le)), amph::r2_word(c->f), c->f);
-  if (flags & AMPH_F_DEVICE) {  // the texts at any byte alignment
-    if (int st = check_dev_words({tuples, out})) return st;
-    if (((uintptr_t)woff | (uintptr_t)toff | (uintptr_t)bad_index) & 7)
-      return fail(AMPH_E_PARAM, "device offset tables and verdict arrays must be 8-byte aligned");
-    if (!c->sub.empty()) c = c->sub[0];
-    HIP_TRY(use_device(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (!(flags & AMPH_F_ACCUMULATE)) HIP_TRY(hipMemsetAsync(bad_index, 0x7F, 8 * K, s));
-    // the word table is the device's: every record takes 37 characters of the
-    // texts, so T <= texts_len / 37 bounds the grid (surplus workgroups exit)
-    const size_t tbound = texts_len / 37 + 1;
-    hipError_t e = amph::launch_convert_share_json_seg(
-        texts, woff, toff, K, amph::wire_tile_grid(tbound, K, amph::kConvTileWords), (const uint4*)tuples, alpha,
-        use_zero, (uint4*)out, (unsigned long long*)bad_index, c->f, cfg(c, s, tbound));
-    return e == hipSuccess ? AMPH_OK : hip_fail(e, "k_conv_json_seg");
-  }
-  if (int st = check_word_table(woff, K)) return st;
-  std::vector<uint64_t> itoff(K);
-  size_t chars = 0;
-  for (size_t o = 0; o < K; ++o) {
-    const uint64_t nc = amph::masked_input_data_chars(woff[o + 1] - woff[o]), end = toff[o] + nc;
-    if (end < toff[o] || end > (uint64_t)texts_len)
-      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": its text [" + std::to_string(toff[o]) + ", " +
-                                    std::to_string(end) + ") runs past the " + std::to_string(texts_len) +
-                                    " characters of the texts");
-    chars += (toff[o] - chars) & 15;  // the image keeps every text's alignment
-    itoff[o] = chars;
-    chars += nc;
-  }
-  if (woff[K] && (!tuples || !out)) return fail(AMPH_E_PARAM, "null tuples/output");
-  UploadPieces io;
-  io.text = [&](size_t o) { return texts + toff[o]; };
-  io.tuples = [&](size_t o) { return tuples + 32 * woff[o]; };
-  io.out = [&](size_t o) { return out + 32 * woff[o]; };
-  return upload_conv_host(c, K, woff, itoff, chars, io, alpha, use_zero, bad_index);
-}
-
-int amph_convert_share_json_batch(amph_ctx* c, const char* const* texts, const size_t* lens, const size_t* words,
-                                  size_t K, const uint8_t* const* tuples, const uint8_t mac_key_le[16],
-                                  int use_zero, uint8_t* const* out, int64_t* bad_index, uint32_t flags) {
-  if (check_ctx(c)) return AMPH_E_PARAM;
-  if (flags) return fail(AMPH_E_PARAM, "the gathered batch calls take host memory only (flags must be 0)");
-  if (K == 0) return AMPH_OK;
-  if (!mac_key_le) return fail(AMPH_E_PARAM, "null mac key");
-  if (!texts || !lens || !words || !tuples || !out || !bad_index)
-    return fail(AMPH_E_PARAM, "null pointer array or verdict array");
-  std::vector<uint64_t> woff(K + 1, 0), itoff(K);
-  size_t chars = 0;
-  for (size_t o = 0; o < K; ++o) {
-    const size_t nc = amph::masked_input_data_chars(words[o]);
-    if (lens[o] != nc)
-      return fail(AMPH_E_LEN, "object " + std::to_string(o) + ": data array text of " + std::to_string(lens[o]) +
-                                  " characters, expected " + std::to_string(nc) + " for " +
-                                  std::to_string(words[o]) + " compact records");
-    if (!texts[o] || (words[o] && (!tuples[o] || !out[o])))
-      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null buffer");
-    woff[o + 1] = woff[o] + words[o];
-    itoff[o] = chars;  // the dense concatenation
-    chars += nc;
-  }
-  const W4 alpha = amph::mont_mul(w4_of(ld128(mac_key_le)), amph::r2_word(c->f), c->f);
-  UploadPieces io;
-  io.text = [&](size_t o) { return texts[o]; };
-  io.tuples = [&](size_t o) { return tuples[o]; };
-  io.out = [&](size_t o) { return out[o]; };
-  return upload_conv_host(c, K, woff.data(), itoff, chars, io, alpha, use_zero, bad_index);
-}
-
-int amph_mask_input_json_packed(amph_ctx* c, const amph_odo_b64* odos, int n, const uint64_t* woff,
-                                const uint64_t* toff, size_t K, const uint8_t* secrets, char* out_text,
-                                size_t out_cap, const uint64_t* ooff, int64_t* first_fail, int64_t* bad_char,
-                                uint32_t flags, void* stream) {
-  if (check_ctx(c)) return AMPH_E_PARAM;
-  AMPH_NO_HOST_IO(flags);
-  if (K == 0) return AMPH_OK;
-  if (int st = wire_batch_parties(odos, n)) return st;
-  if (!woff || !toff || !ooff || !out_text || !first_fail || !bad_char)
-    return fail(AMPH_E_PARAM, "null offsets table, output text or verdict array");
-  for (int j = 1; j < n; ++j)
-    if (odos[j].nchars != odos[0].nchars)
-      return fail(AMPH_E_LEN, "party " + std::to_string(j) + ": field buffers of " + std::to_string(odos[j].nchars) +
-                                  " characters, party 0's hold " + std::to_string(odos[0].nchars));
-  const size_t nchars = odos[0].nchars;
-  if (flags & AMPH_F_DEVICE) {
-    amph::TextSet tx{};
-    for (int j = 0; j < n; ++j)
-      for (int k = 0; k < 5; ++k) {
-        tx.t[k][j] = b64_field(odos[j], k);
-        if (nchars && !tx.t[k][j]) return fail(AMPH_E_PARAM, "null ODO field text");
-        if (int st = check_dev_words({tx.t[k][j]})) return st;
-      }
-    if (int st = check_dev_words({secrets, out_text})) return st;
-    if (((uintptr_t)woff | (uintptr_t)toff | (uintptr_t)ooff | (uintptr_t)first_fail | (uintptr_t)bad_char) & 7)
-      return fail(AMPH_E_PARAM, "device offset tables and verdict arrays must be 8-byte aligned");
-    if (nchars && !secrets) return fail(AMPH_E_PARAM, "null secrets");
-    if (!c->sub.empty()) c = c->sub[0];
-    HIP_TRY(use_device(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (!(flags & AMPH_F_ACCUMULATE)) {
-      HIP_TRY(hipMemsetAsync(first_fail, 0x7F, 8 * K, s));
-      HIP_TRY(hipMemsetAsync(bad_char, 0x7F, 8 * K, s));
-    }
-    // T <= 3 nchars / 64 bounds the grid, as amph_mask_input_b64_packed; the
-    // launch runs for nchars == 0 too: every object is empty and gets its "[]"
-    const size_t tbound = 3 * (nchars / 64) + 3, grid = amph::wire_tile_grid(tbound, K);
-    hipError_t e = amph::launch_mask_json_seg(tx, n, woff, toff, ooff, K, grid, (const uint4*)secrets, out_text,
-                                              (unsigned long long*)first_fail, (unsigned long long*)bad_char,
-                                              c->f, cfg(c, s, tbound));
-    return e == hipSuccess ? AMPH_OK : hip_fail(e, "k_mask_json_seg");
-  }
-  if (int st = check_wire_tables(woff, toff, K, nchars)) return st;
-  for (size_t o = 0; o < K; ++o) {
-    const uint64_t end = ooff[o] + amph::masked_input_data_chars(woff[o + 1] - woff[o]);
-    if (ooff[o] % 16)
-      return fail(AMPH_E_PARAM, "out_text_offsets[" + std::to_string(o) + "] = " + std::to_string(ooff[o]) +
-                                    " must be a multiple of 16");
-    if (end < ooff[o] || end > (o + 1 < K ? ooff[o + 1] : (uint64_t)out_cap))
-      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": its output text [" + std::to_string(ooff[o]) +
-                                    ", " + std::to_string(end) + ") runs past " +
-                                    (o + 1 < K ? "the next slot at " + std::to_string(ooff[o + 1])
-                                               : "the output capacity " + std::to_string(out_cap)));
-  }
-  const size_t T = woff[K];
-  if (T) {
-    for (int j = 0; j < n; ++j)
-      for (int k = 0; k < 5; ++k)
-        if (!b64_field(odos[j], k)) return fail(AMPH_E_PARAM, "null ODO field text");
-    if (!secrets) return fail(AMPH_E_PARAM, "null secrets");
-  }
-  WirePieces io;
-  io.text = [&](int j, int k, size_t o) { return b64_field(odos[j], k) + toff[o]; };
-  io.secrets = [&](size_t o) { return secrets + 16 * woff[o]; };
-  io.out_text = [&](size_t o) { return out_text + ooff[o]; };
-  const size_t used = toff[K - 1] + amph::wire_text_chars(woff[K] - woff[K - 1]);  // the last text's end
-  return wire_batch_host(c, n, K, woff, toff, used, true, false, false, io, first_fail, bad_char, true);
-}
-
-int amph_mask_input_json_batch(amph_ctx* c, const amph_odo_b64* odos, int n, size_t K, const size_t* words,
-                               const uint8_t* const* secrets, char* const* out_texts, int64_t* first_fail,
-                               int64_t* bad_char, uint32_t flags) {
-  if (check_ctx(c)) return AMPH_E_PARAM;
-  if (K && !flags && !out_texts) return fail(AMPH_E_PARAM, "null output text array");
-  return wire_batch_call(c, odos, n, K, words, true, secrets, nullptr, nullptr, first_fail, bad_char, flags,
-                         out_texts);
-}
-
-}  // extern "C"
-
-// ---- many Output Delivery responses per call (include/amphora_respond_batch.h) ----
-// The producer of the slotted field buffers the wire batch calls read: K
-// objects' five packed word arrays through k_odo_b64_seg (codec.hip,
-// respondtiles.hpp).  Host mode as the calls above: ONE page-locked image in
-// -- [word table | text table | reject | 5 word arrays] -- and one back -- the
-// five field buffers up to the last text's end -- scattered text by text, so
-// the caller's gaps stay untouched; a call that fits the small-call arena is
-// built and encoded there in place.  No verdicts: nothing to take back.
-namespace {
-const uint8_t* odo_words(const amph_odo& o, int k) {
-  const uint8_t* const f[5] = {o.secret_shares, o.r_shares, o.v_shares, o.w_shares, o.u_shares};
-  return f[k];
-}
-char* out_field(const amph_odo_b64_out& o, int k) {
-  char* const f[5] = {o.secret_shares, o.r_shares, o.v_shares, o.w_shares, o.u_shares};
-  return f[k];
-}
-
-// The host tables against T words and nchars characters: the wire batch
-// calls' rules, and then the kernel's own geometry -- no object's range is
-// clamped and no tile's text is clipped.
-int check_respond_tables(const uint64_t* woff, const uint64_t* toff, size_t K, uint64_t T, size_t nchars) {
-  if (int st = check_wire_tables(woff, toff, K, nchars)) return st;
-  if (woff[K] != T)
-    return fail(AMPH_E_PARAM, "word_offsets[" + std::to_string(K) + "] = " + std::to_string(woff[K]) +
-                                  " differs from the fields' " + std::to_string(T) + " words");
-  if (T > amph::kRespondMaxWords) return fail(AMPH_E_PARAM, "too many words for one call");
-  for (size_t o = 0; o < K; ++o) {
-    uint64_t w0, W;
-    amph::respond_object_words(woff, o, T, &w0, &W);
-    bool ok = w0 == woff[o] && W == woff[o + 1] - woff[o];
-    if (ok && W) {
-      const size_t last = (size_t)((W - 1) / amph::kWireTileWords);
-      const amph::RespondTile t = amph::respond_tile(woff, toff, o, last, T, nchars);
-      ok = t.words && t.store == t.chars && t.out_char == toff[o] + amph::kRespondTileChars * last &&
-           t.out_char + t.chars == toff[o] + amph::wire_text_chars(W);
-    }
-    if (!ok) return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": its tiles leave the arrays or the buffers");
-  }
-  return AMPH_OK;
-}
-
-struct RespondPieces {  // object o's words of field k, and where its text of field k goes
-  std::function<const uint8_t*(int, size_t)> in;
-  std::function<char*(int, size_t)> out;
-};
-
-// tables validated, T = woff[K] > 0; `used` = the last text's end
-int respond_host(amph_ctx* c, size_t K, const uint64_t* woff, const uint64_t* toff, size_t used,
-                 const RespondPieces& io, const int64_t* reject) {
-  const size_t T = woff[K];
-  if (!c->sub.empty()) c = c->sub[0];
-  std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(use_device(c->device));
-  hipStream_t s;
-  if (int st = host_stream(c, 0, &s)) return st;
-  const size_t fchars = align256(used), fbytes = align256(16 * T);
-  const size_t tab_w = 0, tab_t = tab_w + align256(8 * (K + 1)), rej = tab_t + align256(8 * K);
-  const size_t wrd = rej + (reject ? align256(8 * K) : 0), in_bytes = wrd + 5 * fbytes;
-  const size_t txt = in_bytes, total = txt + 5 * fchars;
-  const bool small = small_call(c, total);
-  uint8_t *himg, *dimg;
-  if (small) {
-    if (c->small.ensure(total + 256) != hipSuccess) return fail(AMPH_E_NOMEM, "small-call arena");
-    himg = dimg = (uint8_t*)c->small.p;
-  } else {
-    if (c->wire_img.ensure(total) != hipSuccess) return fail(AMPH_E_NOMEM, "respond batch image");
-    if (dev_ensure(c, c->wire, total) != hipSuccess) return fail(AMPH_E_NOMEM, "respond staging");
-    himg = (uint8_t*)c->wire_img.p;
-    dimg = (uint8_t*)c->wire.p;
-  }
-  std::memcpy(himg + tab_w, woff, 8 * (K + 1));
-  std::memcpy(himg + tab_t, toff, 8 * K);
-  if (reject) {  // the device's convention: kNoFail = clean
-    unsigned long long* r = (unsigned long long*)(himg + rej);
-    for (size_t o = 0; o < K; ++o) r[o] = reject[o] >= 0 ? (unsigned long long)reject[o] : amph::kNoFail;
-  }
-  const uint8_t* din[5];
-  char* dout[5];
-  for (int k = 0; k < 5; ++k) {
-    for (size_t o = 0; o < K; ++o)
-      if (const size_t w = woff[o + 1] - woff[o])
-        std::memcpy(himg + wrd + k * fbytes + 16 * woff[o], io.in(k, o), 16 * w);
-    din[k] = dimg + wrd + k * fbytes;
-    dout[k] = (char*)(dimg + txt + k * fchars);
-  }
-  if (!small) {  // page-locked image, idle stream: one blocking copy (kPageableRule)
-    HIP_TRY(hipMemcpy(dimg, himg, in_bytes, hipMemcpyHostToDevice));
-    c->respond_copies.fetch_add(1, std::memory_order_relaxed);
-  }
-  hipError_t e = amph::launch_odo_b64_seg(din, dout, (const uint64_t*)(dimg + tab_w), (const uint64_t*)(dimg + tab_t),
-                                          K, amph::wire_tile_grid(T, K), T, used,
-                                          reject ? (const unsigned long long*)(dimg + rej) : nullptr, cfg(c, s, T));
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    return hip_fail(e, "k_odo_b64_seg");
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  if (!small) {
-    HIP_TRY(hipMemcpy(himg + txt, dimg + txt, total - txt, hipMemcpyDeviceToHost));
-    c->respond_copies.fetch_add(1, std::memory_order_relaxed);
-  }
-  for (int k = 0; k < 5; ++k)
-    for (size_t o = 0; o < K; ++o)
-      if (const size_t nc = amph::wire_text_chars(woff[o + 1] - woff[o]))
-        std::memcpy(io.out(k, o), himg + txt + k * fchars + toff[o], nc);
-  return AMPH_OK;
-}
-}  // namespace
-
-extern "C" {
-
-uint64_t amph_respond_batch_copies(const amph_ctx* c) {
-  if (!c) return 0;
-  return (c->sub.empty() ? c : c->sub[0])->respond_copies.load(std::memory_order_relaxed);
-}
-
-int amph_odo_fields_b64_packed(amph_ctx* c, const amph_odo* fields, const uint64_t* woff, const uint64_t* toff,
-                               size_t K, const amph_odo_b64_out* out, const int64_t* reject, uint32_t flags,
-                               void* stream) {
-  if (check_ctx(c)) return AMPH_E_PARAM;
-  AMPH_NO_HOST_IO(flags);
-  if (flags & AMPH_F_ACCUMULATE) return fail(AMPH_E_PARAM, "AMPH_F_ACCUMULATE is not accepted by this call");
-  if (K == 0) return AMPH_OK;
-  if (!fields || !out || !woff || !toff) return fail(AMPH_E_PARAM, "null fields, output or offsets table");
-  if (fields->nbytes % 16) return fail(AMPH_E_LEN, "ODO field length must be a multiple of 16 bytes");
-  const size_t T = fields->nbytes / 16;
-  if (T == 0) return AMPH_OK;
-  for (int k = 0; k < 5; ++k)
-    if (!odo_words(*fields, k) || !out_field(*out, k)) return fail(AMPH_E_PARAM, "null ODO field or output text");
-  if (flags & AMPH_F_DEVICE) {
-    for (int k = 0; k < 5; ++k)
-      if (int st = check_dev_words({odo_words(*fields, k), out_field(*out, k)})) return st;
-    if (((uintptr_t)woff | (uintptr_t)toff | (uintptr_t)reject) & 7)
-      return fail(AMPH_E_PARAM, "device offset tables and verdict arrays must be 8-byte aligned");
-    if (!c->sub.empty()) c = c->sub[0];
-    HIP_TRY(use_device(c->device));
-    const uint8_t* din[5];
-    char* dout[5];
-    for (int k = 0; k < 5; ++k) {
-      din[k] = odo_words(*fields, k);
-      dout[k] = out_field(*out, k);
-    }
-    hipError_t e = amph::launch_odo_b64_seg(din, dout, woff, toff, K, amph::wire_tile_grid(T, K), T, out->nchars,
-                                            (const unsigned long long*)reject, cfg(c, (hipStream_t)stream, T));
-    return e == hipSuccess ? AMPH_OK : hip_fail(e, "k_odo_b64_seg");
-  }
-  if (int st = check_respond_tables(woff, toff, K, T, out->nchars)) return st;
-  RespondPieces io;
-  io.in = [&](int k, size_t o) { return odo_words(*fields, k) + 16 * woff[o]; };
-  io.out = [&](int k, size_t o) { return out_field(*out, k) + toff[o]; };
-  const size_t used = toff[K - 1] + amph::wire_text_chars(woff[K] - woff[K - 1]);  // the last text's end
-  return respond_host(c, K, woff, toff, used, io, reject);
-}
-
-int amph_odo_fields_b64_batch(amph_ctx* c, const amph_odo* odos, size_t K, char* const* out_fields,
-                              const int64_t* reject, uint32_t flags) {
-  if (check_ctx(c)) return AMPH_E_PARAM;
-  if (flags) return fail(AMPH_E_PARAM, "the gathered batch calls take host memory only (flags must be 0)");
-  if (K == 0) return AMPH_OK;
-  if (!odos || !out_fields) return fail(AMPH_E_PARAM, "null ODO array or output text array");
-  std::vector<uint64_t> woff(K + 1, 0), toff(K, 0);
-  size_t chars = 0, used = 0;
-  for (size_t o = 0; o < K; ++o) {
-    if (odos[o].nbytes % 16)
-      return fail(AMPH_E_LEN, "object " + std::to_string(o) + ": ODO fields of " + std::to_string(odos[o].nbytes) +
-                                  " bytes, not a multiple of 16");
-    const size_t w = odos[o].nbytes / 16;
-    for (int k = 0; k < 5 && w; ++k)
-      if (!odo_words(odos[o], k) || !out_fields[5 * o + k])
-        return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null ODO field or output text");
-    woff[o + 1] = woff[o] + w;
-    toff[o] = chars;
-    if (w) used = chars + amph::wire_text_chars(w);
-    chars += amph::wire_slot_chars(w);
-  }
-  if (woff[K] == 0) return AMPH_OK;
-  if (woff[K] > amph::kRespondMaxWords) return fail(AMPH_E_PARAM, "too many words for one call");
-  RespondPieces io;
-  io.in = [&](int k, size_t o) { return odo_words(odos[o], k); };
-  io.out = [&](int k, size_t o) { return out_fields[5 * o + k]; };
-  return respond_host(c, K, woff.data(), toff.data(), used, io, reject);
 }
 
 }  // extern "C"

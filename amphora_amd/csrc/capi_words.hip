@@ -268,7 +268,7 @@ int packed_call(amph_ctx* c, const amph_odo* odos, int n, const uint64_t* offset
   if (int st = packed_words(odos, n, &T)) return st;
   if (!offsets || !first_fail) return fail(AMPH_E_PARAM, "null offsets table or first_fail array");
   if (T && (!out || (masked && !secrets))) return fail(AMPH_E_PARAM, masked ? "null secrets/output" : "null output");
-  if (!c->sub.empty()) c = c->sub[0];  // a multi-device context runs packed calls on its first device
+  c = first_device(c);  // a multi-device context runs packed calls on its first device
   const auto launch = [&](const DevIn& din, const DevOut& dout, size_t cnt, size_t base, const uint64_t* tab,
                           unsigned long long* ff, const amph::LaunchCfg& lc) {
     const amph::OdoSet set = odo_set(din.data(), n);
@@ -378,7 +378,7 @@ int batch_call(amph_ctx* c, const amph_odo* odos, int n, size_t n_objects, bool 
   }
   WordArrays ins;
   for (size_t k = 0; k + 1 < arrays.size(); ++k) ins.push_back(gather_array(arrays[k], false));
-  if (!c->sub.empty()) c = c->sub[0];
+  c = first_device(c);
   std::lock_guard<std::mutex> g(c->mu);
   return run_packed(c, T, ins, {gather_array(arrays.back(), true)}, offsets.data(), n_objects, first_fail,
                     [&](const DevIn& din, const DevOut& dout, size_t cnt, size_t base, const uint64_t* tab,

@@ -26,7 +26,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "amphora_amd", "csrc")
 CAPI = [os.path.join(CSRC, f) for f in ("capi_internal.hpp", "capi_ctx.hip", "capi_pipeline.hip", "capi_words.hip",
-                                        "capi_text.hip", "capi_party.hip")]
+                                        "capi_text.hip", "capi_batch.hip", "capi_party.hip")]
 
 
 def _function_spans(src: str):
