@@ -405,6 +405,17 @@ class Context:
             return ff.value
         return ff  # device tensor: AMPH_NO_FAILURE or index, read by the caller
 
+    def _bad_char_status(self, st, sv, n_secrets, words, bad) -> bool:
+        """AMPH_E_PARAM of amph_mask_input_b64 / _json that reports a bad base64
+        character (the wrapper raises ValueError for it).  Host mode: bad_char
+        is set.  Device mode reports one only with n_secrets > words, after it
+        has waited for the verdicts, and names it in amph_last_error."""
+        if st != AMPH_E_PARAM:
+            return False
+        if not _is_dev(sv):
+            return self._ff_value(bad) >= 0
+        return n_secrets > words and lib.amph_last_error().startswith(b"Illegal base64 character")
+
     def _odo_structs(self, odos):
         n = len(odos)
         arr = (_AmphOdo * n)()
@@ -771,7 +782,7 @@ class Context:
         st = lib.amph_mask_input_b64(self._h, arr, len(texts), words, _ptr(sv), S,
                                      _ptr(o16) if raw else None, _ptr(o24) if records else None,
                                      ffp, badp, flags, stream)
-        if st == AMPH_E_PARAM and not _is_dev(sv) and self._ff_value(bad) >= 0:
+        if self._bad_char_status(st, sv, S, words, bad):
             raise ValueError(lib.amph_last_error().decode())
         self._check(st, allow_verify=True)
         return o16, o24, self._ff_value(ff), self._ff_value(bad)
@@ -791,7 +802,7 @@ class Context:
         bad, badp = self._ff(sv)
         st = lib.amph_mask_input_json(self._h, arr, len(texts), words, _ptr(sv), S, _ptr(out), cap,
                                       ffp, badp, flags, stream)
-        if st == AMPH_E_PARAM and not _is_dev(sv) and self._ff_value(bad) >= 0:
+        if self._bad_char_status(st, sv, S, words, bad):
             raise ValueError(lib.amph_last_error().decode())
         self._check(st, allow_verify=True)
         return (out if _is_dev(sv) else out.tobytes()), self._ff_value(ff), self._ff_value(bad)

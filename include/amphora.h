@@ -50,7 +50,7 @@
  * (AMPH_E_PARAM otherwise): the kernels move them as 16-byte vectors.
  *
  * Threading: host-pointer calls on one context are serialised by an internal
- * mutex; device-pointer calls use no context state and may run concurrently.
+ * mutex; device-pointer calls: "Streams" at the end of this file says which.
  *
  * Errors: functions return AMPH_OK (0) or a negative/positive status below.
  * AMPH_E_VERIFY = the MAC check failed; *first_fail then holds the smallest
@@ -665,6 +665,61 @@ int amph_synth_words(amph_ctx* ctx, uint64_t seed, size_t count, uint8_t* out, v
  * achieves at this size on this GPU, the practical ceiling for K_MASK. */
 int amph_stream_probe(amph_ctx* ctx, const amph_odo* odos, int n_parties, const uint8_t* secrets,
                       size_t words, uint8_t* out, void* stream);
+
+/* ---- Streams: what an AMPH_F_DEVICE call does to its stream -----------------
+ * (this header and its extensions amphora_wire_batch.h, amphora_upload_batch.h
+ * and amphora_respond_batch.h; tests/test_stream_contract.py holds every call
+ * to it with its inputs arriving on a side stream behind the call's return.)
+ *
+ * Order.  Every kernel, memset and copy of a device-mode call, of a *_dev
+ * session call and of amph_synth_* / amph_stream_probe is enqueued on `stream`
+ * (or on work chained to it by events) before the call returns: inputs may
+ * still be in flight on `stream` when the call is made, and work enqueued on
+ * `stream` after the call sees its outputs and verdict words.  Nothing is
+ * issued on the default stream, and a stream created non-blocking is not
+ * ordered against it.
+ *
+ * No wait.  In steady state the call returns without waiting for `stream` or
+ * for the device.  A first call may allocate (hipMalloc; a buffer that grows
+ * is freed first, and hipFree waits for the device): the exchange codec's
+ * scan scratch, a session's buffers when the context's pool has none, the
+ * partner verdict words.  Ragged parties (amph_recombine_verify,
+ * amph_mask_input, amph_recombine_object) take a few staging words from the
+ * device's stream-ordered pool on `stream` (hipMallocAsync / hipFreeAsync): no
+ * wait.  These calls wait for `stream` by design:
+ *   - amph_base64_decode with out_bytes non-null (reads two characters back);
+ *   - amph_mask_input, amph_mask_input_b64 and amph_mask_input_json with
+ *     n_secrets > words (they wait for the verdicts, then return AMPH_E_PARAM
+ *     for a bad character, AMPH_E_VERIFY, or AMPH_E_LEN, as host mode does);
+ *   - amph_party_free (the session's stream) and amph_ctx_destroy.
+ *
+ * Context state.  The device-mode calls take no lock and keep nothing in the
+ * context, so any number of threads may issue them on any streams of one
+ * context at once -- except:
+ *   - amph_exchange_encode / amph_exchange_decode serialise on the context's
+ *     mutex and share ONE scan scratch per context: each call makes `stream`
+ *     wait for the previous device-mode exchange call's kernels, whatever
+ *     stream those ran on, and records an event behind its own.  Exchange
+ *     calls of one context therefore run one after another on the device even
+ *     from different streams, in the order the calls were made; when the
+ *     scratch has to grow, the call first waits on the host for the previous
+ *     exchange call to finish.  A context per stream avoids both.
+ *   - the *_dev session calls serialise on the context's mutex (the buffer
+ *     pool and the session's own state); a session may move between streams
+ *     from call to call, amph_party_finish_b64_dev waits for every accepted
+ *     partner call by event.
+ *
+ * Graph capture (hipStreamBeginCapture on `stream`, one linear chain).
+ * Captured and replayed correctly on inputs rewritten in place (tested):
+ * amph_recombine_verify and amph_mask_input on equal-length parties with
+ * AMPH_F_ACCUMULATE, and amph_recombine_verify_b64 and
+ * amph_recombine_verify_packed, whose verdict resets become memset nodes; the
+ * other calls that only launch kernels and memsets on `stream` are of the
+ * same kind.  NOT for capture: the exchange
+ * codec (a per-context event that outlives the graph, a possible host wait),
+ * ragged parties (stream-ordered allocation), the *_dev sessions (host-side
+ * session state, events across streams) and every call listed above as
+ * waiting for its stream. */
 
 #ifdef __cplusplus
 }

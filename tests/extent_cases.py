@@ -242,6 +242,39 @@ class Plan:
 SURROUNDS = (("S0", "zeros"), ("S1", "hostile"))
 
 
+def check_plan(plan: "Plan", device: bool, st, ins, outs, where: str):
+    """P1-P3 of one run whose arrays have been fetched (ins / outs = {name:
+    Guarded} with `after` set); returns the outputs that have a reference."""
+    want = plan.status[0 if device else 1]
+    assert st == want, "%s: status %d, expected %d" % (where, st, want)             # P1
+    got = {}
+    for a in plan.outs:
+        exp, pay = a.expected(device), outs[a.name].payload()
+        if exp is not None:
+            if pay[:len(exp)] != exp:
+                at = next(i for i in range(len(exp)) if pay[i] != exp[i])
+                raise AssertionError("%s: output %s differs from the reference at byte %d of %d: "
+                                     "0x%02x, expected 0x%02x" % (where, a.name, at, len(exp), pay[at], exp[at]))
+            got[a.name] = pay[:len(exp)]
+        if a.untouched:
+            g = outs[a.name]
+            assert pay == g.before[g.lo:g.lo + g.n].tobytes(), "%s: output %s was written" % (where, a.name)
+        try:
+            outs[a.name].check_untouched()                                           # P2
+        except AssertionError as e:
+            raise AssertionError("%s: %s" % (where, e)) from None
+    if plan.check:
+        whole = {a.name: outs[a.name].payload() for a in plan.outs}
+        plan.check(whole)
+        got.update(whole)
+    for a in plan.ins:
+        try:
+            ins[a.name].check_unchanged()                                            # P3
+        except AssertionError as e:
+            raise AssertionError("%s: %s" % (where, e)) from None
+    return got
+
+
 def run_plan(plan: Plan, device: bool, invoke, sync=None):
     """invoke(ins, outs) -> status, with ins / outs = {name: Guarded}.
     Asserts P1-P4; returns the S0 outputs."""
@@ -258,34 +291,7 @@ def run_plan(plan: Plan, device: bool, invoke, sync=None):
             sync()
         main.fetch()
         aux.fetch()
-        where = "%s [%s]" % (plan.label, sname)
-        want = plan.status[0 if device else 1]
-        assert st == want, "%s: status %d, expected %d" % (where, st, want)             # P1
-        got = {}
-        for a in plan.outs:
-            exp, pay = a.expected(device), outs[a.name].payload()
-            if exp is not None:
-                if pay[:len(exp)] != exp:
-                    at = next(i for i in range(len(exp)) if pay[i] != exp[i])
-                    raise AssertionError("%s: output %s differs from the reference at byte %d of %d: "
-                                         "0x%02x, expected 0x%02x" % (where, a.name, at, len(exp), pay[at], exp[at]))
-                got[a.name] = pay[:len(exp)]
-            if a.untouched:
-                g = outs[a.name]
-                assert pay == g.before[g.lo:g.lo + g.n].tobytes(), "%s: output %s was written" % (where, a.name)
-            try:
-                outs[a.name].check_untouched()                                           # P2
-            except AssertionError as e:
-                raise AssertionError("%s: %s" % (where, e)) from None
-        if plan.check:
-            whole = {a.name: outs[a.name].payload() for a in plan.outs}
-            plan.check(whole)
-            got.update(whole)
-        for a in plan.ins:
-            try:
-                ins[a.name].check_unchanged()                                            # P3
-            except AssertionError as e:
-                raise AssertionError("%s: %s" % (where, e)) from None
+        got = check_plan(plan, device, st, ins, outs, "%s [%s]" % (plan.label, sname))
         seen[sname] = (st, got)
     s0, s1 = seen["S0"], seen["S1"]                                                      # P4
     assert s0[0] == s1[0], "%s: the status depends on the bytes around the inputs" % plan.label

@@ -173,7 +173,7 @@ def test_mask_input_more_secrets_than_masks_verifies_first(ctx, F, torch, fault)
     a tampered set, AMPH_E_LEN only for an honest one -- the reference's
     order (verifyOutputDeliveryObjects :153 before inputMasks.get(i) :160),
     checked against the oracle, in host and device mode and through the
-    fused wire call."""
+    fused wire call in both modes (honest, MAC fault, bad character)."""
     import amphora_amd as A
     W, S = 700, 900
     odos, _ = F.synth_odos(seed=61, n=3, W=W, fault_index=fault)
@@ -182,9 +182,11 @@ def test_mask_input_more_secrets_than_masks_verifies_first(ctx, F, torch, fault)
     assert want == ("verify" if fault >= 0 else "index")
     dodos = [tuple(dev(torch, f) for f in o) for o in odos]
     texts = [tuple(ctx.base64_encode(f.tobytes()) for f in o) for o in odos]
+    dtexts = [tuple(dev(torch, np.frombuffer(bytearray(t), np.uint8)) for t in o) for o in texts]
     calls = [("host", lambda: ctx.mask_input(odos, secrets), lambda ff: ff),
              ("device", lambda: ctx.mask_input(dodos, dev(torch, secrets)), ff_dev),
-             ("b64", lambda: ctx.mask_input_b64(texts, W, secrets, records=True)[2], lambda ff: ff)]
+             ("b64", lambda: ctx.mask_input_b64(texts, W, secrets, records=True)[2], lambda ff: ff),
+             ("b64 device", lambda: ctx.mask_input_b64(dtexts, W, dev(torch, secrets), records=True)[2], ff_dev)]
     for mode, call, ffv in calls:
         if want == "verify":
             r = call()
@@ -194,6 +196,16 @@ def test_mask_input_more_secrets_than_masks_verifies_first(ctx, F, torch, fault)
             with pytest.raises(A.AmphoraNativeError) as e:
                 call()
             assert e.value.status == A._lib.AMPH_E_LEN, mode
+    # a bad character is reported before the MACs and the length, as the
+    # reference decodes before it verifies: the same ValueError in both modes
+    # (device mode waits for the verdicts on this path, include/amphora.h)
+    spoilt = [list(o) for o in texts]
+    spoilt[2][1] = spoilt[2][1][:17] + b"*" + spoilt[2][1][18:]
+    dspoilt = [tuple(dev(torch, np.frombuffer(bytearray(t), np.uint8)) for t in o) for o in spoilt]
+    for mode, call in (("b64", lambda: ctx.mask_input_b64(spoilt, W, secrets, records=True)),
+                       ("b64 device", lambda: ctx.mask_input_b64(dspoilt, W, dev(torch, secrets), records=True))):
+        with pytest.raises(ValueError, match="Illegal base64 character at index 17 of party 2's rShares"):
+            call()
     # the client mirror maps the statuses to the reference's exceptions
     from amphora_amd import client as CL
     from amphora_amd.entities import IntegrityVerificationException, OutputDeliveryObject, Secret
