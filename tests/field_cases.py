@@ -330,7 +330,9 @@ def fault_positions(W: int):
 
 
 def with_fault(odos, index: int):
-    """Copies of the arrays with party 0's w word at `index` off by one."""
+    """Copies of the arrays with party 0's w word at `index` off by one.
+    Faults in y, r, v and u, by other parties, and changes that are no fault
+    mod p are catalogued in tests/verdict_cases.py."""
     out = [tuple(f.copy() for f in o) for o in odos]
     w = out[0][3]
     v = int.from_bytes(w[index].tobytes(), "little")
