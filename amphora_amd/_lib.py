@@ -155,6 +155,15 @@ def _load():
     L.amph_respond_batch_copies.argtypes = [vp]
     L.amph_odo_fields_b64_packed.argtypes = [vp, vp, vp, vp, sz, vp, vp, u32, vp]
     L.amph_odo_fields_b64_batch.argtypes = [vp, vp, sz, pp, vp, u32]
+    # include/amphora_exchange_batch.h
+    L.amph_exchange_slot_chars.restype = sz
+    L.amph_exchange_slot_chars.argtypes = [sz]
+    L.amph_exchange_batch_copies.restype = u64
+    L.amph_exchange_batch_copies.argtypes = [vp]
+    L.amph_exchange_encode_packed.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, u32, vp]
+    L.amph_exchange_decode_packed.argtypes = [vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp, u32, vp]
+    L.amph_exchange_encode_batch.argtypes = [vp, pp, pp, C.POINTER(sz), sz, pp, C.POINTER(sz), vp, u32]
+    L.amph_exchange_decode_batch.argtypes = [vp, pp, C.POINTER(sz), C.POINTER(sz), sz, pp, pp, i64p, u32]
     return L
 
 
@@ -214,6 +223,11 @@ EXPORTED_UPLOAD_BATCH = ["amph_upload_slot_chars", "amph_upload_batch_copies", "
                          "amph_mask_input_json_batch"]
 # what include/amphora_respond_batch.h declares
 EXPORTED_RESPOND_BATCH = ["amph_odo_fields_b64_packed", "amph_odo_fields_b64_batch", "amph_respond_batch_copies"]
+# what include/amphora_exchange_batch.h declares
+EXPORTED_EXCHANGE_BATCH = ["amph_exchange_slot_chars", "amph_exchange_encode_packed", "amph_exchange_encode_batch",
+                           "amph_exchange_decode_packed", "amph_exchange_decode_batch",
+                           "amph_exchange_batch_copies"]
+AMPH_EXCHANGE_SLOT_ALIGN = 8192
 ODO_FIELD_NAMES = ("secretShares", "rShares", "vShares", "wShares", "uShares")
 
 
@@ -235,6 +249,11 @@ def masked_input_data_chars(words: int) -> int:
 def upload_slot_chars(words: int) -> int:
     """amph_upload_slot_chars: that text rounded up to whole 16-byte units."""
     return int(lib.amph_upload_slot_chars(words))
+
+
+def exchange_slot_chars(npairs: int) -> int:
+    """amph_exchange_slot_chars: amph_exchange_max_chars rounded up to AMPH_EXCHANGE_SLOT_ALIGN."""
+    return int(lib.amph_exchange_slot_chars(npairs))
 
 
 def wire_bad_char_message(bad: int, words: int) -> str:
@@ -1249,6 +1268,129 @@ class Context:
             raise ValueError(lib.amph_last_error().decode())
         self._check(st)
         return (mag, neg) if not _is_dev(a) else (mag, neg, bad)
+
+    # -- many requests' exchange texts per call (include/amphora_exchange_batch.h) --
+    def exchange_batch_copies(self) -> int:
+        """amph_exchange_batch_copies: host-device copies of the host-mode calls below."""
+        return int(lib.amph_exchange_batch_copies(self._h))
+
+    def _exchange_result(self, st, res, verdict, status):
+        """The decode's verdicts are its result: AMPH_E_PARAM / AMPH_E_LEN with
+        an offset reported in `verdict` return them (status=True appends
+        (status, amph_last_error)); anything else raises."""
+        msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
+        if not (st in (AMPH_E_PARAM, AMPH_E_LEN) and not _is_dev(verdict) and (np.asarray(verdict) >= 0).any()):
+            self._check(st)
+        return res + ((st, msg),) if status else res
+
+    def exchange_encode_packed(self, mag, neg, pair_offsets, text_offsets=None, out=None, out_lens=None):
+        """amph_exchange_encode_packed: K objects' FactorPair array texts from
+        one call.  mag (T, 2, 16) / neg (T, 2): the objects' diffs (amph_odo_pre's
+        layout, host arrays or device tensors) on pair_offsets[K + 1]; object o's
+        text goes to out[text_offsets[o]:] (multiples of
+        AMPH_EXCHANGE_SLOT_ALIGN; default: the dense layout of
+        exchange_slot_chars strides in a fresh buffer).  Bytes outside the texts
+        are not written.  Returns (out, text_offsets, out_lens): what
+        exchange_decode_packed takes as texts, text_offsets and text_lens."""
+        m = mag if _is_dev(mag) else np.ascontiguousarray(mag, np.uint8)
+        g = neg if _is_dev(neg) else np.ascontiguousarray(neg, np.uint8)
+        flags, stream = self._mode(m, g)
+        T = byte_len(m) // 32
+        K = max(0, len(pair_offsets) - 1)
+        cap = None
+        if text_offsets is None:
+            text_offsets, cap = self._dense_offsets(pair_offsets, exchange_slot_chars)
+        if len(text_offsets) != K:
+            raise ValueError("one text offset per object, one more pair offset")
+        if out is None:
+            if cap is None:
+                raise ValueError("text_offsets of the caller's need the caller's out buffer")
+            out = self._empty(m, (max(16, cap),))
+        if _is_dev(out) != _is_dev(m):
+            raise ValueError("out must live where the diffs live")
+        cap = out.numel() if _is_dev(out) else out.size
+        (po, to), _, _ = self._tables(m, K, (pair_offsets, text_offsets), (), False)
+        if out_lens is None:
+            out_lens = self._empty(m, (max(1, K),), "int64")[:K] if _is_dev(m) else np.zeros(K, np.uint64)
+        st = lib.amph_exchange_encode_packed(self._h, _ptr(m), _ptr(g), T, _ptr(po), _ptr(to), K, _ptr(out), cap,
+                                             _ptr(out_lens), flags, stream)
+        self._check(st)
+        return out, to, out_lens
+
+    def exchange_encode_batch(self, mags, negs, out_caps=None, status=False):
+        """amph_exchange_encode_batch: per object its diffs (host arrays) ->
+        per object its text as bytes, one call for all.  out_caps (testing the
+        capacity rule): a text longer than its out_caps[o] is left out (None in
+        its place) and the call's AMPH_E_LEN returned with status=True."""
+        K = len(mags)
+        if len(negs) != K:
+            raise ValueError("one sign array per magnitude array")
+        ms = [np.ascontiguousarray(x, np.uint8).reshape(-1) for x in mags]
+        gs = [np.ascontiguousarray(x, np.uint8).reshape(-1) for x in negs]
+        nps = [x.size // 32 for x in ms]
+        caps = [int(lib.amph_exchange_max_chars(n)) for n in nps] if out_caps is None else [int(c) for c in out_caps]
+        outs = [np.zeros(max(1, c), np.uint8) for c in caps]
+        lens = np.zeros(max(1, K), np.uint64)
+        szs = lambda xs: (C.c_size_t * max(1, K))(*xs)  # noqa: E731
+        ptrs = lambda xs: (C.c_void_p * max(1, K))(*[x.ctypes.data for x in xs])  # noqa: E731
+        st = lib.amph_exchange_encode_batch(self._h, ptrs(ms), ptrs(gs), szs(nps), K, ptrs(outs), szs(caps),
+                                            lens.ctypes.data, 0)
+        msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
+        if not (st == AMPH_E_LEN and status):
+            self._check(st)
+        texts = [outs[o][:int(lens[o])].tobytes() if int(lens[o]) <= caps[o] else None for o in range(K)]
+        return (texts, lens[:K], (st, msg)) if status else texts
+
+    def exchange_decode_packed(self, texts, pair_offsets, text_offsets, text_lens, bad_index=None, accumulate=False,
+                               status=False, npairs_total=None):
+        """amph_exchange_decode_packed: K texts in one buffer (uint8 array /
+        bytes, or a 1-D uint8 device tensor), object o's text_lens[o] characters
+        at text_offsets[o], expected to hold pair_offsets[o + 1] -
+        pair_offsets[o] pairs.  Returns (mag (T, 2, 16), neg (T, 2),
+        bad_index[K]): host -- -1, the offending byte's offset inside the
+        object's own text, or its length on a count mismatch; device -- int64
+        tensor of AMPH_NO_FAILURE / offset.  A faulty object's own rows are
+        unspecified.  npairs_total: pair_offsets[K], which sizes the outputs; a
+        host table gives it, a device table is never read here (the call stays
+        asynchronous), so it must come with one."""
+        a = self._bytes_view(texts)
+        flags, stream = self._mode(a)
+        n = a.numel() if _is_dev(a) else a.size
+        K = max(0, len(pair_offsets) - 1)
+        if len(text_offsets) != K or len(text_lens) != K:
+            raise ValueError("one text offset and length per object, one more pair offset")
+        if npairs_total is None:
+            if _is_dev(pair_offsets):
+                raise ValueError("a device pair table needs npairs_total: the table is not read on the host")
+            npairs_total = int(pair_offsets[-1]) if K else 0
+        T = int(npairs_total)
+        (po, to, tl), (bad,), acc = self._tables(a, K, (pair_offsets, text_offsets, text_lens), (bad_index,),
+                                                 accumulate)
+        mag = self._empty(a, (T, 2, 16))
+        neg = self._empty(a, (T, 2))
+        st = lib.amph_exchange_decode_packed(self._h, _ptr(a), n, _ptr(po), _ptr(to), _ptr(tl), K, T, _ptr(mag),
+                                             _ptr(neg), _ptr(bad), flags | acc, stream)
+        return self._exchange_result(st, (mag, neg, bad), bad, status)
+
+    def exchange_decode_batch(self, texts, npairs, status=False):
+        """amph_exchange_decode_batch: texts[o] (str / bytes) expected to hold
+        npairs[o] pairs -> (list of (mag (P_o, 2, 16), neg (P_o, 2)),
+        bad_index[K]) -- per object what exchange_decode gives."""
+        K = len(texts)
+        if len(npairs) != K:
+            raise ValueError("one pair count per text")
+        tv = [self._bytes_view(x) for x in texts]
+        if any(_is_dev(x) for x in tv):
+            raise ValueError("the batch calls take host buffers")
+        mags = [np.zeros((int(p), 2, 16), np.uint8) for p in npairs]
+        negs = [np.zeros((int(p), 2), np.uint8) for p in npairs]
+        bad = np.full(K, -1, dtype=np.int64)
+        szs = lambda xs: (C.c_size_t * max(1, K))(*xs)  # noqa: E731
+        ptrs = lambda xs: (C.c_void_p * max(1, K))(*[x.ctypes.data for x in xs])  # noqa: E731
+        st = lib.amph_exchange_decode_batch(self._h, ptrs(tv), szs([x.size for x in tv]),
+                                            szs([int(p) for p in npairs]), K, ptrs(mags), ptrs(negs),
+                                            bad.ctypes.data_as(C.POINTER(C.c_int64)), 0)
+        return self._exchange_result(st, (list(zip(mags, negs)), bad), bad, status)
 
     # -- one party's Output Delivery, device-resident between steps ------------
     def party_begin(self, share_data, share_stride: int, masks32, triples96, n_parties: int,

@@ -1,15 +1,18 @@
 // C ABI of libamphora_hip: the many-objects-per-call families --
 // include/amphora_wire_batch.h (K_RV / K_MASK from K objects' wire texts),
-// include/amphora_upload_batch.h (K MaskedInput uploads, both ends) and
-// include/amphora_respond_batch.h (K Output Delivery responses' fields).
+// include/amphora_upload_batch.h (K MaskedInput uploads, both ends),
+// include/amphora_respond_batch.h (K Output Delivery responses' fields) and
+// include/amphora_exchange_batch.h (K requests' Beaver exchange texts).
 #include "capi_internal.hpp"
 #include "wiretiles.hpp"
 #include "respondtiles.hpp"
+#include "exchangetiles.hpp"
 
 namespace {
 // ---- the host image ---------------------------------------------------------------
 // Host mode of every call here moves ONE image to the device and one back,
-// whatever the object count, around ONE launch: 256-aligned regions, all the
+// whatever the object count, around ONE launch (the exchange codec's: one
+// fixed sequence of launches): 256-aligned regions, all the
 // inputs (tables first) before all the outputs, the verdict words last.
 //   Small (the image fits the small-call arena): it is built in the arena and
 // the kernel reads and writes it in place; the verdict words stay in device
@@ -747,6 +750,296 @@ int amph_odo_fields_b64_batch(amph_ctx* c, const amph_odo* odos, size_t K, char*
   io.in = [&](int k, size_t o) { return odo_words(odos[o], k); };
   io.out = [&](int k, size_t o) { return out_fields[5 * o + k]; };
   return respond_host(c, K, woff.data(), toff.data(), used, io, reject);
+}
+
+}  // extern "C"
+
+// ---- many requests' Beaver exchange texts per call (include/amphora_exchange_batch.h) ----
+// K objects' FactorPair array texts through the segmented codec (exchange.hip,
+// exchangetiles.hpp).  Encode image: [pair table | text table | magnitudes |
+// signs] in, [texts in dense slots | lengths] out.  Decode image: [pair table |
+// text table | lengths | texts in dense slots] in, [magnitudes | signs | K
+// verdict words] out.  The image's own slots are the dense layout whatever
+// the caller's are: texts are gathered and scattered one by one, so the
+// caller's gaps are neither read nor written.  The scans' scratch is
+// c->xstage, device memory in either image mode.
+namespace {
+int check_pair_table(const uint64_t* poff, size_t K, size_t npairs) {
+  if (poff[0] != 0) return fail(AMPH_E_PARAM, "pair_offsets[0] must be 0");
+  for (size_t o = 0; o < K; ++o)
+    if (poff[o + 1] < poff[o])
+      return fail(AMPH_E_PARAM, "pair_offsets must not decrease (entry " + std::to_string(o + 1) + ")");
+  if (poff[K] != npairs)
+    return fail(AMPH_E_PARAM, "pair_offsets[" + std::to_string(K) + "] = " + std::to_string(poff[K]) +
+                                  " differs from npairs_total = " + std::to_string(npairs));
+  if (npairs > ((size_t)1 << 48)) return fail(AMPH_E_PARAM, "too many pairs for one call");
+  return AMPH_OK;
+}
+
+// object o's `chars(o)` characters at toff[o] (a multiple of the span) end
+// before the next slot, which starts later, and before the capacity
+int check_exchange_slots(const uint64_t* toff, size_t K, const std::function<uint64_t(size_t)>& chars, uint64_t cap,
+                         const char* cap_name) {
+  for (size_t o = 0; o < K; ++o) {
+    const uint64_t end = toff[o] + chars(o);
+    const bool next = o + 1 < K;
+    if (toff[o] % AMPH_EXCHANGE_SLOT_ALIGN)
+      return fail(AMPH_E_PARAM, "text_offsets[" + std::to_string(o) + "] = " + std::to_string(toff[o]) +
+                                    " must be a multiple of " + std::to_string(AMPH_EXCHANGE_SLOT_ALIGN));
+    if (end < toff[o] || end > (next ? toff[o + 1] : cap) || (next && toff[o + 1] <= toff[o]))
+      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": its text [" + std::to_string(toff[o]) + ", " +
+                                    std::to_string(end) + ") runs past " +
+                                    (next ? "the next slot at " + std::to_string(toff[o + 1])
+                                          : std::string(cap_name) + " = " + std::to_string(cap)));
+  }
+  return AMPH_OK;
+}
+
+int exchange_scratch(amph_ctx* c, size_t bytes, void** p) {
+  if (dev_ensure(c, c->xstage, bytes) != hipSuccess) return fail(AMPH_E_NOMEM, "exchange scratch");
+  *p = c->xstage.p;
+  return AMPH_OK;
+}
+
+struct XEncPieces {  // object o's diffs, and its text's destination with its capacity
+  std::function<const uint8_t*(size_t)> mag, neg;
+  std::function<char*(size_t)> out;
+  std::function<size_t(size_t)> cap;
+};
+
+// poff validated (poff[K] = T pairs)
+int exchange_encode_host(amph_ctx* c, size_t K, const uint64_t* poff, const XEncPieces& io, uint64_t* out_lens) {
+  const size_t T = poff[K];
+  std::vector<uint64_t> itoff(K);
+  size_t chars = 0;
+  for (size_t o = 0; o < K; ++o) {
+    itoff[o] = chars;
+    chars += amph::xseg_slot_chars(poff[o + 1] - poff[o]);
+  }
+  BatchImage m;
+  const size_t tab_p = m.in(8 * (K + 1)), tab_t = m.in(8 * K), mg = m.in(32 * T + 16), ng = m.in(2 * T + 16);
+  const size_t txt = m.out(chars), lens = m.out(8 * K);
+  if (int st = m.open(c, &amph_ctx::exchange_copies, "exchange")) return st;
+  void* scratch;
+  if (int st = exchange_scratch(m.c, amph::xencs_scratch_bytes(T, K), &scratch)) return st;
+  std::memcpy(m.host(tab_p), poff, 8 * (K + 1));
+  std::memcpy(m.host(tab_t), itoff.data(), 8 * K);
+  for (size_t o = 0; o < K; ++o)
+    if (const size_t P = poff[o + 1] - poff[o]) {
+      std::memcpy(m.host(mg + 32 * poff[o]), io.mag(o), 32 * P);
+      std::memcpy(m.host(ng + 2 * poff[o]), io.neg(o), 2 * P);
+    }
+  if (int st = m.upload()) return st;
+  hipError_t e = amph::launch_exchange_encode_seg((const uint4*)m.dev(mg), m.dev(ng), T, m.dev_table(tab_p),
+                                                  m.dev_table(tab_t), K, (char*)m.dev(txt), chars,
+                                                  (unsigned long long*)m.dev(lens), scratch, cfg(m.c, m.s, T));
+  if (int st = m.finish(e, "k_xencs")) return st;
+  const uint64_t* got = (const uint64_t*)m.host(lens);
+  size_t nshort = 0, first = 0;
+  for (size_t o = 0; o < K; ++o) {
+    out_lens[o] = got[o];
+    if (got[o] > io.cap(o)) {
+      if (!nshort++) first = o;
+      continue;
+    }
+    std::memcpy(io.out(o), m.host(txt + itoff[o]), got[o]);
+  }
+  if (nshort)
+    return fail(AMPH_E_LEN, "object " + std::to_string(first) + ": output capacity " + std::to_string(io.cap(first)) +
+                                " below the encoded length " + std::to_string(got[first]) + " (" +
+                                std::to_string(nshort) + " of " + std::to_string(K) + " texts do not fit)");
+  return AMPH_OK;
+}
+
+struct XDecPieces {  // object o's text, and where its diffs go
+  std::function<const char*(size_t)> text;
+  std::function<uint8_t*(size_t)> mag, neg;
+};
+
+// poff validated; len[o] = object o's characters
+int exchange_decode_host(amph_ctx* c, size_t K, const uint64_t* poff, const std::function<size_t(size_t)>& len,
+                         const XDecPieces& io, int64_t* bad_index) {
+  const size_t T = poff[K];
+  std::vector<uint64_t> itoff(K), ilen(K);
+  size_t chars = 0;
+  for (size_t o = 0; o < K; ++o) {
+    itoff[o] = chars;
+    ilen[o] = len(o);
+    const size_t slot = (ilen[o] + AMPH_EXCHANGE_SLOT_ALIGN - 1) & ~(size_t)(AMPH_EXCHANGE_SLOT_ALIGN - 1);
+    chars += slot ? slot : AMPH_EXCHANGE_SLOT_ALIGN;
+    bad_index[o] = -1;
+  }
+  BatchImage m;
+  const size_t tab_p = m.in(8 * (K + 1)), tab_t = m.in(8 * K), tab_l = m.in(8 * K), txt = m.in(chars);
+  const size_t mg = m.out(32 * T + 16), ng = m.out(2 * T + 16);
+  m.verdicts(K, "verdict array");
+  if (int st = m.open(c, &amph_ctx::exchange_copies, "exchange")) return st;
+  void* scratch;
+  if (int st = exchange_scratch(m.c, amph::xdecs_scratch_bytes(chars, K), &scratch)) return st;
+  std::memcpy(m.host(tab_p), poff, 8 * (K + 1));
+  std::memcpy(m.host(tab_t), itoff.data(), 8 * K);
+  std::memcpy(m.host(tab_l), ilen.data(), 8 * K);
+  for (size_t o = 0; o < K; ++o)
+    if (ilen[o]) std::memcpy(m.host(txt + itoff[o]), io.text(o), ilen[o]);
+  if (int st = m.upload()) return st;  // (resets the verdict words)
+  hipError_t e = amph::launch_exchange_decode_seg((const char*)m.dev(txt), chars, m.dev_table(tab_p),
+                                                  m.dev_table(tab_t), m.dev_table(tab_l), K, T, (uint4*)m.dev(mg),
+                                                  m.dev(ng), m.dverd, false, scratch, cfg(m.c, m.s, chars));
+  if (int st = m.finish(e, "k_xdecs")) return st;
+  const unsigned long long* v = m.verdict_words();
+  size_t nbad = 0, nlen = 0, fb = 0, fl = 0;
+  for (size_t o = 0; o < K; ++o) {
+    const size_t P = poff[o + 1] - poff[o];
+    if (v[o] == amph::kNoFail) {
+      if (P) {
+        std::memcpy(io.mag(o), m.host(mg + 32 * poff[o]), 32 * P);
+        std::memcpy(io.neg(o), m.host(ng + 2 * poff[o]), 2 * P);
+      }
+      continue;
+    }
+    bad_index[o] = (int64_t)v[o];
+    if (v[o] == ilen[o]) {
+      if (!nlen++) fl = o;
+    } else if (!nbad++) {
+      fb = o;
+    }
+  }
+  if (nbad)
+    return fail(AMPH_E_PARAM, "object " + std::to_string(fb) + ": Malformed FactorPair JSON at offset " +
+                                  std::to_string(v[fb]) + " (" + std::to_string(nbad + nlen) + " of " +
+                                  std::to_string(K) + " texts refused)");
+  if (nlen)
+    return fail(AMPH_E_LEN, "object " + std::to_string(fl) + ": interimValues must hold exactly " +
+                                std::to_string(poff[fl + 1] - poff[fl]) + " FactorPairs (" + std::to_string(nlen) +
+                                " of " + std::to_string(K) + " texts refused)");
+  return AMPH_OK;
+}
+
+const char* const kGatherHostOnly = "the gathered batch calls take host memory only (flags must be 0)";
+}  // namespace
+
+extern "C" {
+
+size_t amph_exchange_slot_chars(size_t npairs) { return amph::xseg_slot_chars(npairs); }
+
+uint64_t amph_exchange_batch_copies(const amph_ctx* c) {
+  return c ? first_device(c)->exchange_copies.load(std::memory_order_relaxed) : 0;
+}
+
+int amph_exchange_encode_packed(amph_ctx* c, const uint8_t* mag16, const uint8_t* neg, size_t npairs,
+                                const uint64_t* poff, const uint64_t* toff, size_t K, char* out, size_t out_cap,
+                                uint64_t* out_lens, uint32_t flags, void* stream) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  AMPH_NO_HOST_IO(flags);
+  if (flags & AMPH_F_ACCUMULATE) return fail(AMPH_E_PARAM, "AMPH_F_ACCUMULATE is not accepted by this call");
+  if (K == 0) return AMPH_OK;
+  if (!poff || !toff || !out || !out_lens || (npairs && (!mag16 || !neg)))
+    return fail(AMPH_E_PARAM, "null diffs, offsets table, output text or length array");
+  if (flags & AMPH_F_DEVICE) {
+    if (int st = check_dev_words({mag16, out})) return st;
+    if (int st = tables_misaligned({poff, toff, out_lens})) return st;
+    c = first_device(c);
+    HIP_TRY(use_device(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(c->mu);
+    void* scratch;
+    if (int st = dev_scratch(c, amph::xencs_scratch_bytes(npairs, K), s, &scratch)) return st;
+    hipError_t e = amph::launch_exchange_encode_seg((const uint4*)mag16, neg, npairs, poff, toff, K, out, out_cap,
+                                                    (unsigned long long*)out_lens, scratch, cfg(c, s, npairs));
+    if (e != hipSuccess) return hip_fail(e, "k_xencs");
+    HIP_TRY(hipEventRecord(c->xdev_done, s));
+    return AMPH_OK;
+  }
+  if (int st = check_pair_table(poff, K, npairs)) return st;
+  if (int st = check_exchange_slots(
+          toff, K, [&](size_t o) { return (uint64_t)amph::xseg_max_chars(poff[o + 1] - poff[o]); }, out_cap,
+          "out_cap"))
+    return st;
+  XEncPieces io;
+  io.mag = [&](size_t o) { return mag16 + 32 * poff[o]; };
+  io.neg = [&](size_t o) { return neg + 2 * poff[o]; };
+  io.out = [&](size_t o) { return out + toff[o]; };
+  io.cap = [&](size_t o) { return amph::xseg_max_chars(poff[o + 1] - poff[o]); };
+  return exchange_encode_host(c, K, poff, io, out_lens);
+}
+
+int amph_exchange_encode_batch(amph_ctx* c, const uint8_t* const* mag16, const uint8_t* const* neg,
+                               const size_t* npairs, size_t K, char* const* out, const size_t* out_caps,
+                               uint64_t* out_lens, uint32_t flags) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  if (flags) return fail(AMPH_E_PARAM, kGatherHostOnly);
+  if (K == 0) return AMPH_OK;
+  if (!mag16 || !neg || !npairs || !out || !out_caps || !out_lens)
+    return fail(AMPH_E_PARAM, "null pointer array, capacity array or length array");
+  std::vector<uint64_t> poff(K + 1, 0);
+  for (size_t o = 0; o < K; ++o) {
+    if (!out[o] || (npairs[o] && (!mag16[o] || !neg[o])))
+      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null buffer");
+    poff[o + 1] = poff[o] + npairs[o];
+  }
+  if (int st = check_pair_table(poff.data(), K, poff[K])) return st;
+  XEncPieces io;
+  io.mag = [&](size_t o) { return mag16[o]; };
+  io.neg = [&](size_t o) { return neg[o]; };
+  io.out = [&](size_t o) { return out[o]; };
+  io.cap = [&](size_t o) { return out_caps[o]; };
+  return exchange_encode_host(c, K, poff.data(), io, out_lens);
+}
+
+int amph_exchange_decode_packed(amph_ctx* c, const char* texts, size_t texts_len, const uint64_t* poff,
+                                const uint64_t* toff, const uint64_t* tlen, size_t K, size_t npairs,
+                                uint8_t* mag16, uint8_t* neg, int64_t* bad_index, uint32_t flags, void* stream) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  AMPH_NO_HOST_IO(flags);
+  if (K == 0) return AMPH_OK;
+  if (!poff || !toff || !tlen || !bad_index || (texts_len && !texts) || (npairs && (!mag16 || !neg)))
+    return fail(AMPH_E_PARAM, "null texts, offsets table, diffs or verdict array");
+  if (flags & AMPH_F_DEVICE) {
+    if (int st = check_dev_words({mag16, texts})) return st;
+    if (int st = tables_misaligned({poff, toff, tlen, bad_index})) return st;
+    c = first_device(c);
+    HIP_TRY(use_device(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> g(c->mu);
+    void* scratch;
+    if (int st = dev_scratch(c, amph::xdecs_scratch_bytes(texts_len, K), s, &scratch)) return st;
+    hipError_t e = amph::launch_exchange_decode_seg(texts, texts_len, poff, toff, tlen, K, npairs, (uint4*)mag16, neg,
+                                                    (unsigned long long*)bad_index, !(flags & AMPH_F_ACCUMULATE),
+                                                    scratch, cfg(c, s, texts_len));
+    if (e != hipSuccess) return hip_fail(e, "k_xdecs");
+    HIP_TRY(hipEventRecord(c->xdev_done, s));
+    return AMPH_OK;
+  }
+  if (flags & AMPH_F_ACCUMULATE) return fail(AMPH_E_PARAM, "AMPH_F_ACCUMULATE needs AMPH_F_DEVICE here");
+  if (int st = check_pair_table(poff, K, npairs)) return st;
+  if (int st = check_exchange_slots(toff, K, [&](size_t o) { return tlen[o]; }, texts_len, "texts_len")) return st;
+  XDecPieces io;
+  io.text = [&](size_t o) { return texts + toff[o]; };
+  io.mag = [&](size_t o) { return mag16 + 32 * poff[o]; };
+  io.neg = [&](size_t o) { return neg + 2 * poff[o]; };
+  return exchange_decode_host(c, K, poff, [&](size_t o) { return (size_t)tlen[o]; }, io, bad_index);
+}
+
+int amph_exchange_decode_batch(amph_ctx* c, const char* const* texts, const size_t* lens, const size_t* npairs,
+                               size_t K, uint8_t* const* mag16, uint8_t* const* neg, int64_t* bad_index,
+                               uint32_t flags) {
+  if (check_ctx(c)) return AMPH_E_PARAM;
+  if (flags) return fail(AMPH_E_PARAM, kGatherHostOnly);
+  if (K == 0) return AMPH_OK;
+  if (!texts || !lens || !npairs || !mag16 || !neg || !bad_index)
+    return fail(AMPH_E_PARAM, "null pointer array or verdict array");
+  std::vector<uint64_t> poff(K + 1, 0);
+  for (size_t o = 0; o < K; ++o) {
+    if ((lens[o] && !texts[o]) || (npairs[o] && (!mag16[o] || !neg[o])))
+      return fail(AMPH_E_PARAM, "object " + std::to_string(o) + ": null buffer");
+    poff[o + 1] = poff[o] + npairs[o];
+  }
+  if (int st = check_pair_table(poff.data(), K, poff[K])) return st;
+  XDecPieces io;
+  io.text = [&](size_t o) { return texts[o]; };
+  io.mag = [&](size_t o) { return mag16[o]; };
+  io.neg = [&](size_t o) { return neg[o]; };
+  return exchange_decode_host(c, K, poff.data(), [&](size_t o) { return lens[o]; }, io, bad_index);
 }
 
 }  // extern "C"

@@ -5,7 +5,8 @@
 // calls.  Everything here lives in one namespace of hidden
 // visibility: the library exports only what include/amphora.h and its
 // extension headers include/amphora_wire_batch.h,
-// include/amphora_upload_batch.h and include/amphora_respond_batch.h declare.
+// include/amphora_upload_batch.h, include/amphora_respond_batch.h and
+// include/amphora_exchange_batch.h declare.
 //
 // Host-pointer calls stream the word arrays through the device in batches
 // (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
@@ -35,6 +36,7 @@
 #include "../../include/amphora_wire_batch.h"
 #include "../../include/amphora_upload_batch.h"
 #include "../../include/amphora_respond_batch.h"
+#include "../../include/amphora_exchange_batch.h"
 #include "host_stream.hpp"
 #include "kernels.hpp"
 
@@ -147,6 +149,7 @@ struct amph_ctx {
   std::atomic<uint64_t> wire_copies{0};
   std::atomic<uint64_t> upload_copies{0};  // the same of amphora_upload_batch.h's calls (amph_upload_batch_copies)
   std::atomic<uint64_t> respond_copies{0};  // and of amphora_respond_batch.h's (amph_respond_batch_copies)
+  std::atomic<uint64_t> exchange_copies{0};  // and of amphora_exchange_batch.h's (amph_exchange_batch_copies)
   DevBuf xstage;  // host-mode staging of the exchange codec calls
   DevBuf xdev;    // device-mode scan scratch of the exchange codec calls
   hipEvent_t xdev_done = nullptr;  // the last device-mode exchange call's kernels
@@ -349,6 +352,10 @@ struct Stager {
 // the verdict word of an exchange decode (`pairs` FactorPairs expected in
 // `len` characters) as the call's status and message (capi_text.hip)
 int decode_status(int64_t bad, size_t len, size_t pairs, int64_t* bad_index);
+// the device-mode exchange calls' scratch: `bytes` of the context's buffer,
+// behind the previous such call's kernels on `s` (capi_text.hip; call under
+// the context mutex and record c->xdev_done after the launches)
+int dev_scratch(amph_ctx* c, size_t bytes, hipStream_t s, void** p);
 
 // ---- the base64 wire texts (capi_text.hip; the batch calls of capi_batch.hip) ----
 extern const char* const kOdoFieldNames[5];

@@ -166,6 +166,23 @@ int decode_status(int64_t bad, size_t len, size_t pairs, int64_t* bad_index) {
   return fail(AMPH_E_PARAM, "Malformed FactorPair JSON at offset " + std::to_string(bad));
 }
 
+// Device-pointer calls of the exchange codec (the single calls here, the
+// many-objects calls of capi_batch.hip) take their scan scratch from one
+// per-context buffer: under the context mutex each call makes its stream wait
+// for the previous call's kernels (xdev_done) before reusing it, then records
+// its own.  (The device's stream-ordered pool handed two contexts overlapping
+// buffers in the host paths)
+int dev_scratch(amph_ctx* c, size_t bytes, hipStream_t s, void** p) {
+  if (!c->xdev_done) HIP_TRY(hipEventCreateWithFlags(&c->xdev_done, hipEventDisableTiming));
+  else HIP_TRY(hipStreamWaitEvent(s, c->xdev_done, 0));
+  if (c->xdev.cap < bytes) {
+    HIP_TRY(hipEventSynchronize(c->xdev_done));  // the old buffer is idle before it is freed
+    if (dev_ensure(c, c->xdev, bytes) != hipSuccess) return fail(AMPH_E_NOMEM, "exchange scratch");
+  }
+  *p = c->xdev.p;
+  return AMPH_OK;
+}
+
 const char* const kOdoFieldNames[5] = {"secretShares", "rShares", "vShares", "wShares", "uShares"};
 
 const char* b64_field(const amph_odo_b64& o, int k) {
@@ -188,26 +205,9 @@ int check_parties(const amph_odo_b64* odos, int n) {
 extern "C" {
 
 // ---- Beaver open exchange codec ------------------------------------------------
-namespace {
 // Host-pointer calls of the exchange codec: one shot on the context's first
 // stream (the whole text is scanned at once, so there is no batching).
-//
-// Device-pointer calls take their scan scratch from one per-context buffer:
-// under the context mutex each call makes its stream wait for the previous
-// call's kernels (xdev_done) before reusing it, then records its own.  (The
-// device's stream-ordered pool handed two contexts overlapping buffers in
-// the host paths)
-int dev_scratch(amph_ctx* c, size_t bytes, hipStream_t s, void** p) {
-  if (!c->xdev_done) HIP_TRY(hipEventCreateWithFlags(&c->xdev_done, hipEventDisableTiming));
-  else HIP_TRY(hipStreamWaitEvent(s, c->xdev_done, 0));
-  if (c->xdev.cap < bytes) {
-    HIP_TRY(hipEventSynchronize(c->xdev_done));  // the old buffer is idle before it is freed
-    if (dev_ensure(c, c->xdev, bytes) != hipSuccess) return fail(AMPH_E_NOMEM, "exchange scratch");
-  }
-  *p = c->xdev.p;
-  return AMPH_OK;
-}
-}  // namespace
+// Device-pointer calls take their scan scratch with dev_scratch (above).
 
 size_t amph_exchange_max_chars(size_t npairs) { return amph::xenc_max_bytes(npairs); }
 

@@ -33,6 +33,7 @@
 
 #include "kernels.hpp"
 #include "decimal.hpp"
+#include "exchangetiles.hpp"
 
 namespace amph {
 
@@ -295,6 +296,17 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_apply(uint64_t* x, size_t n
   if (blockIdx.x + 1 == gridDim.x && threadIdx.x == 0) x[n] = sbase[1];
 }
 
+// Decimal digits of a 128-bit magnitude (1 for zero) from its bit length and
+// one compare with a power of ten; p10 = kPow10 staged in LDS.
+__device__ __forceinline__ int ndigits_p10(const uint4& m, const uint4* p10) {
+  const int bits = m.w ? 128 - __clz(m.w) : m.z ? 96 - __clz(m.z) : m.y ? 64 - __clz(m.y) : 32 - __clz(m.x);
+  const int t = (bits * 1233) >> 12;
+  const uint4 p = p10[t];
+  const uint32_t pa[4] = {p.x, p.y, p.z, p.w};
+  const int n = t + (ge128(m, pa) ? 1 : 0);
+  return n ? n : 1;
+}
+
 // Encode pass 1: the text length of each workgroup's run of entries
 // (bs[g] = sum of the entry lengths of pairs [256 g, 256 g + 256)); digit
 // counts from the bit length (ndigits128), not the base-10^8 split.
@@ -320,14 +332,7 @@ __global__ __launch_bounds__(4 * kXBlock) void k_xenc_bsum(const uint4* mag, con
   __syncthreads();
   uint32_t len = 0;
   if (k < npairs) {  // {"a":A,"b":B} (+ ',' unless last)
-    auto nd = [&](const uint4& m) {
-      const int bits = m.w ? 128 - __clz(m.w) : m.z ? 96 - __clz(m.z) : m.y ? 64 - __clz(m.y) : 32 - __clz(m.x);
-      const int t = (bits * 1233) >> 12;
-      const uint4 p = p10[t];
-      const uint32_t pa[4] = {p.x, p.y, p.z, p.w};
-      const int n = t + (ge128(m, pa) ? 1 : 0);
-      return n ? n : 1;
-    };
+    auto nd = [&](const uint4& m) { return ndigits_p10(m, p10); };
     len = 11 + nd(d) + ((ng & 0xFFu) != 0 && !is_zero(d)) + nd(e) + ((ng >> 8) != 0 && !is_zero(e)) +
           (k + 1 < npairs);
   }
@@ -970,28 +975,21 @@ struct SpanBases {
   __device__ __forceinline__ uint64_t total() const { return bscan[nb] & kCountMask; }
 };
 
-template <class Bases>
-__global__ __launch_bounds__(kDecBlock) void k_xdec_slow(Text text, Bases bs, size_t nb,
-                                                     size_t nvals, uint4* mag, uint8_t* neg,
-                                                     unsigned long long* bad,
-                                                     const unsigned int* slow) {
-  if (blockIdx.x == 0) array_check(text, bs.total(), nvals, bad);
-  bs.windows();
-  if (bs.skip(slow)) return;  // the compact pass held
+// One span of the general pass, by one workgroup of kDecBlock lanes: the
+// values of span `span` of `text`, the first of them value gbase of the
+// text's nvals, into mag / neg (the text's own rows) and *bad.  Ends with a
+// barrier, so a workgroup may go on to another span.  (k_xdec_slow's spans,
+// and k_xdecs_slow's: there every span has its own object's text.)
+__device__ __forceinline__ void xdec_general_span(const Text& text, size_t span, uint64_t gbase, size_t nvals,
+                                                  uint4* mag, uint8_t* neg, unsigned long long* bad) {
   __shared__ uint4 win4[kWin / 16 + 1];
   __shared__ uint16_t pos[kMaxStarts];   // start, relative to b0
   __shared__ uint16_t endp[kMaxStarts];  // one past the last digit, relative to w0
   __shared__ uint16_t comma[kMaxStarts]; // member 1: one past the last byte before its ',', rel. w0
   __shared__ uint8_t keyc[kMaxStarts];   // 'a' / 'b', 0 if the number failed its own checks
-  __shared__ uint64_t sbase;
-  for (size_t span = blockIdx.x; span < nb; span += gridDim.x) {
   const size_t b0 = span * kDecSpan;
   const long long w0 = (long long)b0 - kWinPad;
   for (int c = threadIdx.x; c < kWin / 16 + 1; c += kDecBlock) win4[c] = text.chunk(w0 + 16LL * c);
-  if (threadIdx.x < 64) {
-    const uint64_t b = bs.base(span);
-    if (threadIdx.x == 0) sbase = b;
-  }
   __syncthreads();
   const uint8_t* win = reinterpret_cast<const uint8_t*>(win4);
   const Window t{text, win, (size_t)w0};
@@ -1008,7 +1006,6 @@ __global__ __launch_bounds__(kDecBlock) void k_xdec_slow(Text text, Bases bs, si
   }
   __syncthreads();
   const uint32_t nloc = min(total, (uint32_t)kMaxStarts);
-  const uint64_t gbase = sbase;
   // phase 1: own checks + value
   const uint32_t* l32 = reinterpret_cast<const uint32_t*>(win4);
   for (uint32_t idx = threadIdx.x; idx < nloc; idx += kDecBlock) {
@@ -1134,7 +1131,18 @@ __global__ __launch_bounds__(kDecBlock) void k_xdec_slow(Text text, Bases bs, si
     }
   }
   __syncthreads();  // the next span reuses the LDS arrays
-  }
+}
+
+template <class Bases>
+__global__ __launch_bounds__(kDecBlock) void k_xdec_slow(Text text, Bases bs, size_t nb,
+                                                     size_t nvals, uint4* mag, uint8_t* neg,
+                                                     unsigned long long* bad,
+                                                     const unsigned int* slow) {
+  if (blockIdx.x == 0) array_check(text, bs.total(), nvals, bad);
+  bs.windows();
+  if (bs.skip(slow)) return;  // the compact pass held
+  for (size_t span = blockIdx.x; span < nb; span += gridDim.x)
+    xdec_general_span(text, span, bs.base(span), nvals, mag, neg, bad);
 }
 
 // Pass 3 (optimistic): the same staging and colon listing, then one value
@@ -1271,6 +1279,264 @@ __global__ __launch_bounds__(kDecBlock) void k_xdec_span(Text text, uint64_t* cn
   if (threadIdx.x == 0) cnt[span] = total | (sfail ? kWsBit : 0);
 }
 
+// ---- many objects per call (include/amphora_exchange_batch.h) ------------------------
+// The segmented forms of the passes above; who owns what is exchangetiles.hpp's.
+// Encode: one 256-pair tile per workgroup, never across two objects; the
+// tiles' text lengths are scanned over the whole grid, so an object's text
+// starts at scan[its first tile] and a tile's run at scan[tile] - that.
+static_assert(kXBlock == (int)kXTilePairs && kXEntry == (int)kXEntryMax && kDecSpan == kXSlotAlign,
+              "exchangetiles.hpp states this file's tile, entry and span");
+
+__global__ __launch_bounds__(kXBlock) void k_xencs_bsum(const uint4* mag, const uint8_t* neg,
+                                                    const uint64_t* pair_offsets, size_t n_objects,
+                                                    uint64_t npairs, uint64_t* bs) {
+  __shared__ uint32_t ws[kXBlock / 64];
+  __shared__ uint4 p10[39];
+  if (threadIdx.x < 39)
+    p10[threadIdx.x] = make_uint4(kPow10[threadIdx.x][0], kPow10[threadIdx.x][1], kPow10[threadIdx.x][2],
+                                  kPow10[threadIdx.x][3]);
+  const XEncTile t = xenc_tile(pair_offsets, n_objects, npairs, blockIdx.x);
+  const bool on = t.owns && threadIdx.x < t.pairs;
+  const uint64_t k = t.pair0 + threadIdx.x;
+  uint4 d = make_uint4(0, 0, 0, 0), e = d;
+  uint32_t ng = 0;
+  if (on) {
+    d = mag[2 * k];
+    e = mag[2 * k + 1];
+    ng = reinterpret_cast<const uint16_t*>(neg)[k];
+  }
+  __syncthreads();
+  uint32_t len = 0;
+  if (on)  // {"a":A,"b":B} (+ ',' unless the object's last)
+    len = 11 + ndigits_p10(d, p10) + ((ng & 0xFFu) != 0 && !is_zero(d)) + ndigits_p10(e, p10) +
+          ((ng >> 8) != 0 && !is_zero(e)) + (k + 1 < t.last);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) len += __shfl_xor(len, o, 64);
+  if (__lane_id() == 0) ws[threadIdx.x >> 6] = len;
+  __syncthreads();
+  if (threadIdx.x == 0) bs[blockIdx.x] = (uint64_t)ws[0] + ws[1] + ws[2] + ws[3];  // (idle: 0)
+}
+
+// k_xenc_write over one object's tile: the same conversion, placement and
+// LDS-staged 16-byte stores; the object's first tile also writes its
+// brackets and its length.  bs: the scanned tile lengths (grid + 1 words).
+__global__ __launch_bounds__(kXBlock) void k_xencs_write(const uint4* mag, const uint8_t* neg,
+                                                     const uint64_t* pair_offsets,
+                                                     const uint64_t* text_offsets, size_t n_objects,
+                                                     uint64_t npairs, const uint64_t* bs, char* out,
+                                                     uint64_t out_cap, unsigned long long* out_lens) {
+  __shared__ uint4 bufv[(kXBlock * kXEntry + 8) / 16 + 2];
+  char* buf = reinterpret_cast<char*>(bufv);
+  const XEncTile t = xenc_tile(pair_offsets, n_objects, npairs, blockIdx.x);
+  if (!t.owns) return;  // (the whole workgroup)
+  const bool on = threadIdx.x < t.pairs;
+  const uint64_t k = t.pair0 + threadIdx.x;
+  uint32_t cd[5], ce[5];
+  int nd = 0, ne = 0;
+  bool sd = false, se = false;
+  uint32_t len = 0, total;
+  for (int q = threadIdx.x; q < (int)(sizeof(bufv) / 16); q += kXBlock) bufv[q] = make_uint4(0, 0, 0, 0);
+  if (on) {
+    const uint4 d = mag[2 * k], e = mag[2 * k + 1];
+    const uint32_t ng = reinterpret_cast<const uint16_t*>(neg)[k];
+    nd = to_chunks(d, cd);
+    ne = to_chunks(e, ce);
+    sd = (ng & 0xFFu) != 0 && !is_zero(d);
+    se = (ng >> 8) != 0 && !is_zero(e);
+    len = 11 + nd + sd + ne + se + (k + 1 < t.last);
+  }
+  const uint32_t loc = block_excl_scan32(len, &total);
+  const uint64_t obase = bs[t.base_tile], toff = text_offsets[t.object];
+  const uint64_t at = xenc_store_at(toff, bs[blockIdx.x] - obase, total, out_cap);
+  const bool room = at != ~(uint64_t)0;  // (always, under the tables' contract)
+  char* dst = out + (room ? at : 0);
+  const size_t sh = (uintptr_t)dst & 15;
+  if (on) {
+    char* o = buf + sh + loc;
+    o = put_str(o, "{\"a\":");
+    if (sd) *o++ = '-';
+    o = put_digits(o, cd, nd);
+    o = put_str(o, ",\"b\":");
+    if (se) *o++ = '-';
+    o = put_digits(o, ce, ne);
+    *o++ = '}';
+    if (k + 1 < t.last) *o = ',';
+  }
+  __syncthreads();
+  if (room) {
+    char* dal = dst - sh;  // 16-aligned; bytes [sh, sh + total) of it are this run
+    const size_t endb = sh + total;
+    const size_t ulo = sh ? 1 : 0, uhi = endb / 16;  // whole 16-byte units [ulo, uhi)
+    if (uhi <= ulo) {
+      if (sh + threadIdx.x < endb) dal[sh + threadIdx.x] = buf[sh + threadIdx.x];
+    } else {
+      if (sh + threadIdx.x < 16 * ulo) dal[sh + threadIdx.x] = buf[sh + threadIdx.x];
+      for (size_t u = ulo + threadIdx.x; u < uhi; u += kXBlock)
+        xst16(reinterpret_cast<uint4*>(dal) + u, bufv[u]);
+      if (16 * uhi + threadIdx.x < endb) dal[16 * uhi + threadIdx.x] = buf[16 * uhi + threadIdx.x];
+    }
+  }
+  if (t.first && threadIdx.x == 0) {
+    const uint64_t chars = bs[t.base_tile + t.tiles] - obase;  // the object's entries
+    const uint64_t close = xenc_store_at(toff, chars, 0, out_cap);
+    if (close != ~(uint64_t)0) {
+      out[toff] = '[';
+      out[close] = ']';
+    }
+    out_lens[t.object] = chars + 2;
+  }
+}
+
+// Decode: every 8 KiB span of the buffer lies in at most one object's slot;
+// its workgroup builds that object's own Text, so the window either side, the
+// first / last value rules and the array check see what the single call sees
+// on that text alone.  The rest of a slot and the gaps read as whitespace
+// (Text::chunk) and are never loaded.
+struct XDecTables {
+  const uint8_t* texts;  // 16-byte aligned
+  const uint64_t *text_offsets, *text_lens, *pair_offsets;
+  size_t n_objects;
+  uint64_t npairs, texts_len;
+  __device__ __forceinline__ XDecSpan span(size_t s) const {
+    return xdec_span(text_offsets, text_lens, pair_offsets, n_objects, npairs, texts_len, s);
+  }
+  __device__ __forceinline__ Text text(const XDecSpan& d) const { return Text{texts + d.text0, 0, (size_t)d.len}; }
+};
+
+// the verdicts to the sentinel (unless the call accumulates) and the
+// objects' general-pass flags to 0
+__global__ __launch_bounds__(256) void k_xdecs_init(unsigned long long* bad, unsigned int* slow, size_t n_objects,
+                                                int reset) {
+  const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (o >= n_objects) return;
+  slow[o] = 0;
+  if (reset) bad[o] = kNoFail;
+}
+
+// Pass 1, one wave per span as k_xdec_count (no colon list: the parse lists
+// its own): bsum[span] = the span's colons, 0 for a span in no text;
+// whitespace in a span wholly inside its text raises the object's flag.
+__global__ __launch_bounds__(64 * kCntWaves) void k_xdecs_count(XDecTables a, uint64_t* bsum, size_t nb,
+                                                              unsigned int* slow) {
+  const size_t span = (size_t)blockIdx.x * kCntWaves + (threadIdx.x >> 6);
+  if (span >= nb) return;
+  const uint32_t lane = threadIdx.x & 63;
+  const XDecSpan d = a.span(span);
+  if (!d.owns) {
+    if (lane == 0) bsum[span] = 0;
+    return;
+  }
+  const Text t = a.text(d);
+  const size_t base = d.local * kDecSpan + (size_t)lane * 16;
+  const bool whole = (d.local + 1) * kDecSpan <= t.L;
+  uint4 c[8];
+  if (whole) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(t.al + base + 1024 * k));
+      c[k] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = t.chunk((long long)(base + 1024 * k));
+  }
+  uint32_t cnt = 0, low = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    cnt += __popc(colons16(c[k]));
+    low |= swar_below21(c[k].x) | swar_below21(c[k].y) | swar_below21(c[k].z) | swar_below21(c[k].w);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  const bool ws = whole && __ballot(low != 0) != 0;
+  if (lane == 0) {
+    bsum[span] = cnt;
+    if (ws) atomicOr(&slow[d.object], 1u);
+  }
+}
+
+// Pass 3 (optimistic), k_xdec_fast on the span's own object: the window, the
+// colons listed from LDS (as k_xdec_span), one value per lane against its
+// compact segment with its index INSIDE THE OBJECT (the scanned count minus
+// the count at the object's first span).  Anything else raises the object's
+// flag, and k_xdecs_slow parses that object alone with the general grammar.
+__global__ __launch_bounds__(kDecBlock) void k_xdecs_fast(XDecTables a, const uint64_t* bscan, uint4* mag,
+                                                      uint8_t* neg, unsigned int* slow) {
+  const XDecSpan d = a.span(blockIdx.x);
+  if (!d.owns) return;
+  __shared__ uint4 win4[kWin / 16 + 1];
+  __shared__ uint16_t pos[kMaxStarts];  // colon, relative to b0
+  __shared__ uint32_t p10[8];
+  __shared__ unsigned int general;  // one read for the workgroup: other workgroups raise the flag meanwhile
+  if (threadIdx.x == 0) general = slow[d.object];
+  if (threadIdx.x < 8) p10[threadIdx.x] = pow10_small(threadIdx.x);
+  __syncthreads();
+  if (general != 0) return;  // (whitespace seen, or a span already failed: the general pass does the object)
+  const Text text = a.text(d);
+  const size_t b0 = d.local * kDecSpan;
+  const long long w0 = (long long)b0 - kWinPad;
+  if (w0 >= 0 && w0 + 16LL * (kWin / 16 + 1) <= (long long)text.L) {
+    const u32x4* p = reinterpret_cast<const u32x4*>(text.al + w0);
+    const int c2 = min((int)threadIdx.x + 2 * kDecBlock, kWin / 16);
+    const u32x4 v0 = __builtin_nontemporal_load(p + threadIdx.x),
+                v1 = __builtin_nontemporal_load(p + threadIdx.x + kDecBlock), v2 = __builtin_nontemporal_load(p + c2);
+    __builtin_amdgcn_sched_barrier(0);
+    win4[threadIdx.x] = make_uint4(v0.x, v0.y, v0.z, v0.w);
+    win4[threadIdx.x + kDecBlock] = make_uint4(v1.x, v1.y, v1.z, v1.w);
+    if ((int)threadIdx.x + 2 * kDecBlock <= kWin / 16) win4[c2] = make_uint4(v2.x, v2.y, v2.z, v2.w);
+  } else {
+    for (int c = threadIdx.x; c < kWin / 16 + 1; c += kDecBlock) win4[c] = text.chunk(w0 + 16LL * c);
+  }
+  __syncthreads();
+  const int lo = kWinPad + kDecBytes * threadIdx.x;
+  const uint4 c0 = win4[lo / 16], c1 = win4[lo / 16 + 1];
+  const uint32_t w[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+  uint32_t m = colons32(w);
+  uint32_t total;
+  const uint32_t first = block_excl_scan32(__popc(m), &total);
+  for (int k = (int)first; m && k < kMaxStarts; m &= m - 1, ++k)
+    pos[k] = (uint16_t)(kDecBytes * threadIdx.x + __ffs(m) - 1);
+  __syncthreads();
+  const uint64_t gbase = bscan[blockIdx.x] - bscan[d.span0];
+  bool fail = total > (uint32_t)kMaxStarts;
+  const uint32_t nloc = min(total, (uint32_t)kMaxStarts);
+  const uint32_t* l32 = reinterpret_cast<const uint32_t*>(win4);
+  uint4* omag = mag + d.row0;
+  uint8_t* oneg = neg + d.row0;
+  for (uint32_t idx = threadIdx.x; idx < nloc; idx += kDecBlock) {
+    const uint32_t at = pos[idx];
+    const uint64_t g = gbase + idx;
+    FastNum fn;
+    if (g < d.nvals && fast_segment(l32, p10, at + 1 + kWinPad, g, (size_t)d.nvals, b0 + at + 1, (size_t)d.len, fn)) {
+      const size_t slot = (g & ~(uint64_t)1) + (fn.key == 'b');
+      xst16(omag + slot, make_uint4(fn.v[0], fn.v[1], fn.v[2], fn.v[3]));
+      oneg[slot] = fn.minus && (fn.v[0] | fn.v[1] | fn.v[2] | fn.v[3]) != 0;
+    } else {
+      fail = true;
+    }
+  }
+  if (__ballot(fail) != 0 && __lane_id() == 0) atomicOr(&slow[d.object], 1u);
+}
+
+// Pass 4: every object's bracket-and-count check (the workgroup of its first
+// span), and the general pass over the spans of the objects whose flag is up.
+__global__ __launch_bounds__(kDecBlock) void k_xdecs_slow(XDecTables a, const uint64_t* bscan, size_t nb, uint4* mag,
+                                                      uint8_t* neg, unsigned long long* bad,
+                                                      const unsigned int* slow) {
+  for (size_t span = blockIdx.x; span < nb; span += gridDim.x) {
+    const XDecSpan d = a.span(span);
+    if (!d.owns) continue;
+    const Text text = a.text(d);
+    const uint64_t v0 = bscan[d.span0];
+    if (d.local == 0) {
+      array_check(text, bscan[d.span0 + d.spans] - v0, (size_t)d.nvals, bad + d.object);
+      __syncthreads();  // (its LDS words, before the next object's)
+    }
+    if (slow[d.object] == 0) continue;
+    xdec_general_span(text, d.local, bscan[span] - v0, (size_t)d.nvals, mag + d.row0, neg + d.row0, bad + d.object);
+  }
+}
+
 unsigned blocks_of(size_t n, size_t per) { return (unsigned)((n + per - 1) / per); }
 
 // exclusive scan of x[0..n) in place, x[n] = total; bsum: blocks_of(n)+1 scratch
@@ -1378,6 +1644,81 @@ hipError_t launch_exchange_decode(const char* text, size_t len, size_t npairs, u
   return hipGetLastError();
 }
 
+
+// ---- many objects per call -----------------------------------------------------------
+namespace {
+// scan_u64 in its two-launch form whatever n >= 1 is: the batch calls' launch
+// count does not depend on their size
+hipError_t scan_u64_fixed(uint64_t* x, size_t n, uint64_t* bsum, LaunchCfg c) {
+  const unsigned nb = blocks_of(n, kScanBlock);
+  LaunchCfg c0 = c, c2 = c;
+  c0.ev_stop = nullptr;
+  c2.ev_start = nullptr;
+  AMPH_LAUNCH(k_scan_reduce, dim3(nb), dim3(kScanBlock), c0, x, n, bsum);
+  AMPH_LAUNCH(k_scan_apply, dim3(nb), dim3(kScanBlock), c2, x, n, bsum, (size_t)nb, (uint4*)nullptr, (size_t)0);
+  return hipGetLastError();
+}
+}  // namespace
+
+size_t xencs_scratch_bytes(size_t npairs, size_t n_objects) {
+  const size_t nt = xenc_tile_grid(npairs, n_objects);
+  return 8 * (nt + 1) + 8 * ((size_t)blocks_of(nt, kScanBlock) + 1);
+}
+
+// Four launches: the tiles' lengths, their scan (two), the write.
+hipError_t launch_exchange_encode_seg(const uint4* mag, const uint8_t* neg, size_t npairs,
+                                      const uint64_t* pair_offsets, const uint64_t* text_offsets,
+                                      size_t n_objects, char* out, size_t out_cap, unsigned long long* out_lens,
+                                      void* scratch, const LaunchCfg& c) {
+  const size_t nt = xenc_tile_grid(npairs, n_objects);
+  if (n_objects == 0 || nt > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  uint64_t* bs = static_cast<uint64_t*>(scratch);
+  LaunchCfg c0 = c, cm = c, c1 = c;
+  c0.ev_stop = nullptr;
+  cm.ev_start = cm.ev_stop = nullptr;
+  c1.ev_start = nullptr;
+  AMPH_LAUNCH(k_xencs_bsum, dim3((unsigned)nt), dim3(kXBlock), c0, mag, neg, pair_offsets, n_objects,
+              (uint64_t)npairs, bs);
+  hipError_t e = scan_u64_fixed(bs, nt, bs + nt + 1, cm);
+  if (e != hipSuccess) return e;
+  AMPH_LAUNCH(k_xencs_write, dim3((unsigned)nt), dim3(kXBlock), c1, mag, neg, pair_offsets, text_offsets, n_objects,
+              (uint64_t)npairs, (const uint64_t*)bs, out, (uint64_t)out_cap, out_lens);
+  return hipGetLastError();
+}
+
+size_t xdecs_scratch_bytes(size_t texts_len, size_t n_objects) {
+  const size_t nb = xdec_span_grid(texts_len);
+  return 8 * (nb + 1) + 8 * ((size_t)blocks_of(nb, kScanBlock) + 1) + 4 * n_objects + 8;
+}
+
+// Six launches: the verdicts and flags, the count, its scan (two), the
+// compact pass, the checks and the general pass.  One general-pass flag PER
+// OBJECT (n_objects words of scratch): a text with whitespace or a fault sends
+// its own spans through the general grammar and no other object's.
+hipError_t launch_exchange_decode_seg(const char* texts, size_t texts_len, const uint64_t* pair_offsets,
+                                      const uint64_t* text_offsets, const uint64_t* text_lens, size_t n_objects,
+                                      size_t npairs, uint4* mag, uint8_t* neg, unsigned long long* bad,
+                                      bool reset_bad, void* scratch, const LaunchCfg& c) {
+  const size_t nb = xdec_span_grid(texts_len);
+  if (n_objects == 0 || nb > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  const XDecTables a{reinterpret_cast<const uint8_t*>(texts), text_offsets, text_lens, pair_offsets, n_objects,
+                     (uint64_t)npairs, (uint64_t)texts_len};
+  uint64_t* bscan = static_cast<uint64_t*>(scratch);
+  uint64_t* bsum = bscan + nb + 1;
+  unsigned int* slow = reinterpret_cast<unsigned int*>(bsum + blocks_of(nb, kScanBlock) + 1);
+  LaunchCfg c0 = c, cm = c, c1 = c;
+  c0.ev_stop = nullptr;
+  cm.ev_start = cm.ev_stop = nullptr;
+  c1.ev_start = nullptr;
+  AMPH_LAUNCH(k_xdecs_init, dim3(blocks_of(n_objects, 256)), dim3(256), c0, bad, slow, n_objects, (int)reset_bad);
+  AMPH_LAUNCH(k_xdecs_count, dim3(blocks_of(nb, kCntWaves)), dim3(64 * kCntWaves), cm, a, bscan, nb, slow);
+  hipError_t e = scan_u64_fixed(bscan, nb, bsum, cm);
+  if (e != hipSuccess) return e;
+  AMPH_LAUNCH(k_xdecs_fast, dim3((unsigned)nb), dim3(kDecBlock), cm, a, (const uint64_t*)bscan, mag, neg, slow);
+  AMPH_LAUNCH(k_xdecs_slow, dim3((unsigned)std::min<size_t>(nb, kSlowGrid)), dim3(kDecBlock), c1, a,
+              (const uint64_t*)bscan, nb, mag, neg, bad, (const unsigned int*)slow);
+  return hipGetLastError();
+}
 
 static_assert(kDecSpan == kXSpanBytes, "span form: one decode workgroup per span");
 

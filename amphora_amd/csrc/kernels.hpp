@@ -198,6 +198,26 @@ size_t xdec_spans_scratch_bytes(size_t len);
 hipError_t launch_exchange_decode_spans(const char* text, size_t len, size_t npairs, const XSpans& out,
                                         unsigned long long* bad, void* scratch, const LaunchCfg& c);
 
+// Many objects' exchange texts per call (include/amphora_exchange_batch.h;
+// exchangetiles.hpp): the diffs of object o are pairs [pair_offsets[o],
+// pair_offsets[o + 1]) of the packed arrays, its text lies at text_offsets[o]
+// (a multiple of 8192) of ONE 16-byte-aligned buffer.  Device tables; a fixed
+// number of launches whatever n_objects >= 1 is.
+//   encode: out_lens[o] = the text's length; nothing of out[0, out_cap) outside
+// the texts is written.
+//   decode: bad[o] min-combines object o's first offending offset inside its
+// own text (text_lens[o] on a count mismatch); reset_bad: set to kNoFail first.
+size_t xencs_scratch_bytes(size_t npairs, size_t n_objects);
+hipError_t launch_exchange_encode_seg(const uint4* mag, const uint8_t* neg, size_t npairs,
+                                      const uint64_t* pair_offsets, const uint64_t* text_offsets,
+                                      size_t n_objects, char* out, size_t out_cap, unsigned long long* out_lens,
+                                      void* scratch, const LaunchCfg& c);
+size_t xdecs_scratch_bytes(size_t texts_len, size_t n_objects);
+hipError_t launch_exchange_decode_seg(const char* texts, size_t texts_len, const uint64_t* pair_offsets,
+                                      const uint64_t* text_offsets, const uint64_t* text_lens, size_t n_objects,
+                                      size_t npairs, uint4* mag, uint8_t* neg, unsigned long long* bad,
+                                      bool reset_bad, void* scratch, const LaunchCfg& c);
+
 // Synthetic honest n-party ODOs (bench/test input generator, device-side).
 struct OutSet {
   uint4* f[5][kMaxParties];

@@ -272,6 +272,49 @@ class OutputDeliveryService:
                 raise AmphoraServiceException("Failed to open values for operation #%s" % op_id) from e
         return mags, negs
 
+    def _open_many(self, reqs, out):
+        """_open (exchange_format="json") for many requests: reqs = {o: (op_id,
+        mag, neg)}.  One batch encode writes every request's body, the exchange
+        callback runs once per request (the protocol is per operation id), one
+        batch decode parses every partner body of every request -- the objects
+        in partner-major order.  Returns {o: (mags, negs)} as _open's; a request
+        whose exchange, partner body or operation id fails gets out[o] = the
+        AmphoraServiceException _open raises, and the others are unaffected."""
+        from . import wire
+        order = sorted(reqs)
+        bodies = wire.exchange_bodies_to_json(self._ctx, [reqs[o][0] for o in order], self.player_id,
+                                              [reqs[o][1] for o in order], [reqs[o][2] for o in order])
+        partners, failed = {}, {}
+        for o, own in zip(order, bodies):
+            self.last_exchange_object = own
+            try:
+                partners[o] = list(self._exchange(own))
+            except Exception as e:  # noqa: BLE001 -- this request's own outcome
+                failed[o] = e
+        items = [(j, o) for j in range(max([len(p) for p in partners.values()] or [0]))
+                 for o in order if o in partners and j < len(partners[o])]
+        got = wire.exchange_bodies_from_json(self._ctx, [partners[o][j] for j, o in items],
+                                             [reqs[o][1].shape[0] for _, o in items])
+        opened = {o: ([reqs[o][1]], [reqs[o][2]]) for o in partners}
+        for (j, o), res in zip(items, got):
+            if o in failed:
+                continue
+            if isinstance(res, Exception):
+                failed[o] = res
+            elif res[0] != reqs[o][0]:
+                failed[o] = ValueError("operation id %s != %s" % (res[0], reqs[o][0]))
+            else:
+                _check_partner(res[2], reqs[o][1])  # (the decode's pair count fixes the shape: as _open, for the record)
+                opened[o][0].append(res[2])
+                opened[o][1].append(res[3])
+        for o, e in failed.items():
+            opened.pop(o, None)
+            try:
+                raise AmphoraServiceException("Failed to open values for operation #%s" % reqs[o][0]) from e
+            except AmphoraServiceException as x:
+                out[o] = x
+        return opened
+
     def _compute(self, share_words, stride, request_id):
         W = share_words.shape[0]
         masks = self._download(request_id, INPUT_MASK_GFP, 2 * W)
@@ -324,7 +367,9 @@ class OutputDeliveryService:
         and the exchange stay per request (they are the protocol's own), one
         K_ODO_PRE and one open + K_ODO_POST launch run over the concatenation of
         the requests' words -- both are word by word, so every request's ODO is
-        bit for bit the single function's.  Returns one entry per request: the
+        bit for bit the single function's.  With exchange_format="json" the
+        requests' bodies are written by one batch encode and all their
+        partners' bodies parsed by one batch decode (_open_many).  Returns one entry per request: the
         OutputDeliveryObject, or the AmphoraServiceException the single function
         raises for that request (the others are unaffected).
         exchange_format="session" is one request by construction: a loop."""
@@ -361,12 +406,16 @@ class OutputDeliveryService:
                                               np.concatenate([got[o][0] for o in live]),
                                               np.concatenate([got[o][2] for o in live]))
         opened = {}
-        for o in live:  # the exchange works on this request's slice of the packed diffs
-            a, b = 2 * off[o], 2 * (off[o] + words[o].shape[0])
-            try:
-                opened[o] = self._open(got[o][1], mag[a:b], neg[a:b])
-            except AmphoraServiceException as e:
-                out[o] = e
+        cut = {o: (2 * off[o], 2 * (off[o] + words[o].shape[0])) for o in live}
+        if self._json:  # one encode and one decode call for all the requests' bodies
+            opened = self._open_many({o: (got[o][1], mag[a:b], neg[a:b]) for o, (a, b) in cut.items()}, out)
+        else:
+            for o in live:  # the exchange works on this request's slice of the packed diffs
+                a, b = cut[o]
+                try:
+                    opened[o] = self._open(got[o][1], mag[a:b], neg[a:b])
+                except AmphoraServiceException as e:
+                    out[o] = e
         groups = {}  # by party count: one open + K_ODO_POST launch each (one group, unless a partner list is off)
         for o in sorted(opened):
             groups.setdefault(len(opened[o][0]), []).append(o)

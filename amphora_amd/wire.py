@@ -424,3 +424,41 @@ def exchange_from_json(ctx: _lib.Context, text, npairs: int):
     op, pid, lb, rb = _exchange_split(text)
     mag, neg = ctx.exchange_decode(text[lb:rb + 1], npairs)
     return op, pid, mag, neg
+
+
+def exchange_bodies_to_json(ctx: _lib.Context, op_ids, player_id: int, mags, negs) -> List[bytes]:
+    """exchange_to_json for K requests' diffs (host arrays): the K
+    MultiplicationExchangeObject bodies, their interimValues arrays written by
+    ONE encode call (amph_exchange_encode_batch)."""
+    if not (len(op_ids) == len(mags) == len(negs)):
+        raise ValueError("one operation id and one sign array per magnitude array")
+    texts = ctx.exchange_encode_batch(list(mags), list(negs))
+    return [exchange_body(op, player_id, t) for op, t in zip(op_ids, texts)]
+
+
+def exchange_bodies_from_json(ctx: _lib.Context, bodies, npairs_list) -> list:
+    """exchange_from_json for K bodies, their interimValues arrays parsed by
+    ONE decode call (amph_exchange_decode_batch).  One entry per body:
+    (operationId, playerId, mag (P, 2, 16), neg (P, 2)), or the exception
+    exchange_from_json raises for that body -- the others are unaffected."""
+    if len(bodies) != len(npairs_list):
+        raise ValueError("one pair count per body")
+    out, heads = [None] * len(bodies), {}
+    for o, body in enumerate(bodies):
+        try:
+            text = body.encode() if isinstance(body, str) else bytes(body)
+            op, pid, lb, rb = _exchange_split(text)
+            heads[o] = (op, pid, text[lb:rb + 1])
+        except Exception as e:  # noqa: BLE001 -- this body's own outcome
+            out[o] = e
+    live = sorted(heads)
+    if live:
+        res, bad = ctx.exchange_decode_batch([heads[o][2] for o in live], [int(npairs_list[o]) for o in live])
+        for (m, g), b, o in zip(res, bad, live):
+            if b < 0:
+                out[o] = (heads[o][0], heads[o][1], m, g)
+            elif int(b) == len(heads[o][2]):  # the single call's messages (capi_text.hip decode_status)
+                out[o] = ValueError("interimValues must hold exactly %d FactorPairs" % int(npairs_list[o]))
+            else:
+                out[o] = ValueError("Malformed FactorPair JSON at offset %d" % int(b))
+    return out

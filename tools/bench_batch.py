@@ -5,6 +5,8 @@ and what batching buys ("Packed calls").
     python tools/bench_batch.py --wire [--variant-lib LIB] [--reps R] [--out FILE]
     python tools/bench_batch.py --upload [--reps R] [--out FILE]
     python tools/bench_batch.py --respond [--reps R] [--out FILE]
+    python tools/bench_batch.py --exchange [--reps R] [--out FILE]
+    python tools/bench_batch.py --exchange-single --parent-lib LIB [--parent-lib-copy LIB2] [--reps R] [--out FILE]
 
 GPU only (fails without a device).  Everything is warmed up, then timed in
 alternating order within this one process; one JSON line with the build id.
@@ -57,6 +59,25 @@ include/amphora_respond_batch.h), same method, one run on one board:
 * hot path at ONE object of the same 256,000 words, kernel time: k_odo_b64_seg
   against the SUM of the five k_b64_encode_blk launches amph_base64_encode makes
   for the five fields, that sum taken twice per round (a, a2: the spread).
+
+--exchange measures the many-requests exchange codec calls (DESIGN.md section
+4c'''', include/amphora_exchange_batch.h), same method, one run on one board:
+
+* batching: 256 objects x 2,000 pairs of full-length diffs, 3 parties' worth of
+  texts per round (one encode, two partners' decodes).  One
+  amph_exchange_encode_packed and two amph_exchange_decode_packed calls
+  against 256 amph_exchange_encode and 512 amph_exchange_decode calls, device
+  mode (one synchronise per side) and host mode.
+* hot path at ONE object of 512,000 pairs, kernel time from the call's first
+  launch to its last: each packed call against its single call, the single
+  call twice per round (a, a2: the spread).
+
+--exchange-single measures what the many-requests change costs the SINGLE
+exchange calls: amph_exchange_encode / amph_exchange_decode at 8 Mi pairs from
+this tree's library and from another build's (--parent-lib: the parent
+commit's libamphora_hip.so, built from a checkout of it) loaded side by side,
+rows rotating through the round, the other build twice per round, and with
+--parent-lib-copy the same bytes loaded once more from another path.
 """
 import argparse
 import ctypes as C
@@ -84,6 +105,11 @@ ap.add_argument("--out", default=None, help="also write the JSON line to this fi
 ap.add_argument("--wire", action="store_true", help="the many-secrets wire-text calls (section 4c')")
 ap.add_argument("--upload", action="store_true", help="the many-uploads calls (section 4c'')")
 ap.add_argument("--respond", action="store_true", help="the many-responses call (section 4c''')")
+ap.add_argument("--exchange", action="store_true", help="the many-requests exchange codec calls (section 4c'''')")
+ap.add_argument("--exchange-single", action="store_true",
+                help="the single exchange calls at 8 Mi pairs, this tree against --parent-lib")
+ap.add_argument("--parent-lib", default=None, help="--exchange-single: another build's libamphora_hip.so")
+ap.add_argument("--parent-lib-copy", default=None, help="--exchange-single: a copy of --parent-lib under another path")
 ap.add_argument("--variant-lib", default=None, help="--wire: a library built with -DAMPH_WIRE_SEG_LANES=0")
 a = ap.parse_args()
 
@@ -686,6 +712,274 @@ def respond_mode():
 
     emit(result)
 
+
+# ---------------------------------------------------------------- --exchange
+def exchange_mode():
+    """256 objects x 2,000 pairs of full-length diffs, 3 parties' worth of
+    texts per round (one encode, two partners' decodes): the batch calls
+    against 256 (+ 512) single calls, device and host mode, wall clock with one
+    synchronise per side.  Then ONE object of 512,000 pairs: the batch call's
+    kernel time against the single call's, rows a / batch / a2 alternating."""
+    F_DEV = _lib.AMPH_F_DEVICE
+    stream = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+
+    def ok(st):
+        if st != 0:
+            raise RuntimeError(L.amph_last_error().decode())
+
+    def diffs(seed, pairs):
+        mag = ctx.synth_words(seed, 2 * pairs).reshape(pairs, 2, 16)  # field elements: 38-39 digits each
+        neg = (ctx.synth_words(seed + 1, (2 * pairs + 15) // 16).reshape(-1)[:2 * pairs] & 1).reshape(pairs, 2)
+        return mag.contiguous(), neg.contiguous()
+
+    K, PO, PARTNERS = 256, 2000, 2
+    T = K * PO
+    sl, mx = _lib.exchange_slot_chars(PO), int(L.amph_exchange_max_chars(PO))
+    breps = max(5, a.reps // 2)
+    result = {"tool": "bench_batch --exchange", "build_id": _lib.check_build_id(),
+              "device": torch.cuda.get_device_name(0), "board": board_identity(), "reps": a.reps,
+              "warmup": a.warmup, "objects": K, "pairs_per_object": PO, "partner_texts_per_object": PARTNERS,
+              "batching_reps": breps,
+              "timing": {"batching": "wall clock, one synchronise per side", "hot_path": "kernel dispatch events"}}
+    mag, neg = diffs(41, T)
+    hmag, hneg = mag.cpu().numpy(), neg.cpu().numpy()
+    poff = torch.arange(0, T + 1, PO, dtype=torch.int64, device="cuda")
+    toff = torch.arange(0, K * sl, sl, dtype=torch.int64, device="cuda")
+    hpoff, htoff = poff.cpu().numpy().astype(np.uint64), toff.cpu().numpy().astype(np.uint64)
+    text_p = torch.zeros(K * sl, dtype=torch.uint8, device="cuda")
+    text_s = torch.zeros(K * sl, dtype=torch.uint8, device="cuda")
+    lens_p = torch.zeros(K, dtype=torch.int64, device="cuda")
+    lens_s = torch.zeros(K, dtype=torch.int64, device="cuda")
+    omag_p, omag_s = torch.zeros_like(mag), torch.zeros_like(mag)
+    oneg_p, oneg_s = torch.zeros_like(neg), torch.zeros_like(neg)
+    bad_p = torch.zeros(K, dtype=torch.int64, device="cuda")
+    bad_s = torch.zeros(K, dtype=torch.int64, device="cuda")
+    htext_p, htext_s = np.zeros(K * sl, np.uint8), np.zeros(K * sl, np.uint8)
+    hlens_p, hlens_s = np.zeros(K, np.uint64), np.zeros(K, np.uint64)
+    homag_p, homag_s = np.zeros_like(hmag), np.zeros_like(hmag)
+    honeg_p, honeg_s = np.zeros_like(hneg), np.zeros_like(hneg)
+    hbad_p, hbad_s = np.zeros(K, np.int64), np.zeros(K, np.int64)
+    hl = []  # the texts' lengths on the host, once the first encode has run
+
+    def dev_packed():
+        ok(L.amph_exchange_encode_packed(ctx._h, mag.data_ptr(), neg.data_ptr(), T, poff.data_ptr(), toff.data_ptr(),
+                                         K, text_p.data_ptr(), K * sl, lens_p.data_ptr(), F_DEV, stream))
+        for _ in range(PARTNERS):
+            ok(L.amph_exchange_decode_packed(ctx._h, text_p.data_ptr(), K * sl, poff.data_ptr(), toff.data_ptr(),
+                                             lens_p.data_ptr(), K, T, omag_p.data_ptr(), oneg_p.data_ptr(),
+                                             C.cast(C.c_void_p(bad_p.data_ptr()), i64p), F_DEV, stream))
+        torch.cuda.synchronize()
+
+    def dev_singles():
+        for o in range(K):
+            ok(L.amph_exchange_encode(ctx._h, mag.data_ptr() + 32 * PO * o, neg.data_ptr() + 2 * PO * o, PO,
+                                      text_s.data_ptr() + sl * o, mx, lens_s.data_ptr() + 8 * o, F_DEV, stream))
+        for _ in range(PARTNERS):
+            for o in range(K):
+                ok(L.amph_exchange_decode(ctx._h, text_s.data_ptr() + sl * o, hl[o], PO,
+                                          omag_s.data_ptr() + 32 * PO * o, oneg_s.data_ptr() + 2 * PO * o,
+                                          C.cast(C.c_void_p(bad_s.data_ptr() + 8 * o), i64p), F_DEV, stream))
+        torch.cuda.synchronize()
+
+    def host_packed():
+        ok(L.amph_exchange_encode_packed(ctx._h, hmag.ctypes.data, hneg.ctypes.data, T, hpoff.ctypes.data,
+                                         htoff.ctypes.data, K, htext_p.ctypes.data, K * sl, hlens_p.ctypes.data, 0,
+                                         None))
+        for _ in range(PARTNERS):
+            ok(L.amph_exchange_decode_packed(ctx._h, htext_p.ctypes.data, K * sl, hpoff.ctypes.data,
+                                             htoff.ctypes.data, hlens_p.ctypes.data, K, T, homag_p.ctypes.data,
+                                             honeg_p.ctypes.data, hbad_p.ctypes.data_as(i64p), 0, None))
+
+    def host_singles():
+        for o in range(K):
+            ok(L.amph_exchange_encode(ctx._h, hmag.ctypes.data + 32 * PO * o, hneg.ctypes.data + 2 * PO * o, PO,
+                                      htext_s.ctypes.data + sl * o, mx, hlens_s.ctypes.data + 8 * o, 0, None))
+        for _ in range(PARTNERS):
+            for o in range(K):
+                ok(L.amph_exchange_decode(ctx._h, htext_s.ctypes.data + sl * o, int(hlens_s[o]), PO,
+                                          homag_s.ctypes.data + 32 * PO * o, honeg_s.ctypes.data + 2 * PO * o,
+                                          hbad_s[o:].ctypes.data_as(i64p), 0, None))
+
+    dev_packed()
+    hl.extend(int(x) for x in lens_p.cpu().numpy())
+    names = ["device_%d_single_calls" % (K * (1 + PARTNERS)), "device_packed_calls",
+             "host_%d_single_calls" % (K * (1 + PARTNERS)), "host_packed_calls"]
+    bat = alternate(dict(zip(names, (dev_singles, dev_packed, host_singles, host_packed))), breps, 3, wall_ms)
+    NFV = 0x7F7F7F7F7F7F7F7F
+    assert torch.equal(lens_p, lens_s) and torch.equal(omag_p, omag_s) and torch.equal(oneg_p, oneg_s)
+    assert bool((bad_p == NFV).all()) and bool((bad_s == NFV).all())
+    tp, ts = text_p.cpu().numpy(), text_s.cpu().numpy()
+    for o in range(K):
+        lo, hi = sl * o, sl * o + hl[o]
+        assert np.array_equal(tp[lo:hi], ts[lo:hi]) and np.array_equal(htext_p[lo:hi], ts[lo:hi])
+    assert np.array_equal(omag_p.cpu().numpy(), hmag) and np.array_equal(homag_p, hmag) and np.array_equal(homag_s, hmag)
+    assert (hbad_p == -1).all() and (hbad_s == -1).all() and np.array_equal(hlens_p, hlens_s)
+    bat["speedup"] = {"device: singles / packed": ratio(bat, names[0], names[1]),
+                      "host: singles / packed": ratio(bat, names[2], names[3])}
+    bat["device_quartile_ranges_disjoint"] = bool(bat[names[1]]["p75_ms"] < bat[names[0]]["p25_ms"])
+    bat["host_quartile_ranges_disjoint"] = bool(bat[names[3]]["p75_ms"] < bat[names[2]]["p25_ms"])
+    result["batching"] = bat
+
+    # ---- hot path: ONE object of 512,000 pairs, kernel time of the whole call (first launch to last)
+    P1 = 512000
+    m1, g1 = diffs(51, P1)
+    cap1 = _lib.exchange_slot_chars(P1)
+    t_seg = torch.zeros(cap1, dtype=torch.uint8, device="cuda")
+    t_one = torch.zeros(cap1, dtype=torch.uint8, device="cuda")
+    p1 = torch.tensor([0, P1], dtype=torch.int64, device="cuda")
+    z1 = torch.zeros(1, dtype=torch.int64, device="cuda")
+    l_seg, l_one = torch.zeros(1, dtype=torch.int64, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+    om_seg, om_one = torch.zeros_like(m1), torch.zeros_like(m1)
+    on_seg, on_one = torch.zeros_like(g1), torch.zeros_like(g1)
+    b_seg, b_one = torch.zeros(1, dtype=torch.int64, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def enc_one():
+        ok(L.amph_exchange_encode(ctx._h, m1.data_ptr(), g1.data_ptr(), P1, t_one.data_ptr(), cap1, l_one.data_ptr(),
+                                  F_DEV, stream))
+
+    def enc_seg():
+        ok(L.amph_exchange_encode_packed(ctx._h, m1.data_ptr(), g1.data_ptr(), P1, p1.data_ptr(), z1.data_ptr(), 1,
+                                         t_seg.data_ptr(), cap1, l_seg.data_ptr(), F_DEV, stream))
+    enc_one()
+    enc_seg()
+    torch.cuda.synchronize()
+    n1 = int(l_one.item())
+    assert n1 == int(l_seg.item()) and torch.equal(t_one[:n1], t_seg[:n1])
+
+    def dec_one():
+        ok(L.amph_exchange_decode(ctx._h, t_one.data_ptr(), n1, P1, om_one.data_ptr(), on_one.data_ptr(),
+                                  C.cast(C.c_void_p(b_one.data_ptr()), i64p), F_DEV, stream))
+
+    def dec_seg():
+        ok(L.amph_exchange_decode_packed(ctx._h, t_seg.data_ptr(), cap1, p1.data_ptr(), z1.data_ptr(),
+                                         l_seg.data_ptr(), 1, P1, om_seg.data_ptr(), on_seg.data_ptr(),
+                                         C.cast(C.c_void_p(b_seg.data_ptr()), i64p), F_DEV, stream))
+    rows = {"exchange_encode_a": enc_one, "exchange_encode_packed_1_object": enc_seg, "exchange_encode_a2": enc_one,
+            "exchange_decode_a": dec_one, "exchange_decode_packed_1_object": dec_seg, "exchange_decode_a2": dec_one}
+    hot = alternate(rows, a.reps, a.warmup, kernel_ms)
+    assert torch.equal(om_one, om_seg) and torch.equal(on_one, on_seg) and torch.equal(om_one, m1)
+    assert int(b_one.item()) == NFV and int(b_seg.item()) == NFV
+    hot["difference_us"] = {}
+    for k in ("encode", "decode"):
+        base = hot["exchange_%s_a" % k]["median_ms"]
+        hot["difference_us"]["%s: packed minus single" % k] = round(
+            1e3 * (hot["exchange_%s_packed_1_object" % k]["median_ms"] - base), 3)
+        hot["difference_us"]["%s: single a2 minus a (spread)" % k] = round(
+            1e3 * (hot["exchange_%s_a2" % k]["median_ms"] - base), 3)
+    hot["text_chars"] = n1
+    result["hot_path_one_object_of_%d_pairs" % P1] = hot
+    emit(result)
+
+
+def exchange_single_mode():
+    """--exchange-single --parent-lib LIB [--parent-lib-copy LIB2]: the SINGLE
+    calls amph_exchange_encode / amph_exchange_decode at 8 Mi pairs, this
+    tree's library against another build's (the parent commit's, built from a
+    checkout of it) loaded beside it in this process.  Kernel time of the whole
+    call; every row takes every place in the round in turn; the other build
+    twice per round (a, a2: its own spread) and, with --parent-lib-copy, a
+    byte-for-byte copy of it under another path loaded a third time: what two
+    loads of the same code differ by (their own contexts and scratch)."""
+    if not a.parent_lib:
+        sys.exit("--exchange-single needs --parent-lib")
+    vp, sz, i32, u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
+
+    def load(path):
+        lib = C.CDLL(os.path.abspath(path))
+        lib.amph_ctx_create.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, i32, C.POINTER(vp)]
+        lib.amph_ctx_destroy.argtypes = [vp]
+        lib.amph_exchange_encode.argtypes = [vp, vp, vp, sz, vp, sz, vp, u32, vp]
+        lib.amph_exchange_decode.argtypes = [vp, vp, sz, sz, vp, vp, i64p, u32, vp]
+        lib.amph_time_next_launch.argtypes = [vp, vp]
+        lib.amph_timing_event_create.argtypes = [C.POINTER(vp)]
+        lib.amph_timing_event_elapsed_ms.argtypes = [vp, vp, C.POINTER(C.c_float)]
+        lib.amph_build_id.restype = C.c_char_p
+        lib.amph_last_error.restype = C.c_char_p
+        h = vp()
+        keys = [_lib.le16(x) for x in (TEST_PRIME, TEST_R, TEST_RINV)]
+        assert lib.amph_ctx_create(*keys, 0, C.byref(h)) == 0, lib.amph_last_error()
+        return lib, h
+
+    def events(lib):
+        e0, e1 = vp(), vp()
+        assert lib.amph_timing_event_create(C.byref(e0)) == 0 and lib.amph_timing_event_create(C.byref(e1)) == 0
+        return e0, e1
+
+    builds = {"this tree": (L, ctx._h, events(L))}
+    lib, h = load(a.parent_lib)
+    builds["parent"] = (lib, h, events(lib))
+    parent_id = lib.amph_build_id().decode()
+    if a.parent_lib_copy:
+        lib, h = load(a.parent_lib_copy)
+        assert lib.amph_build_id().decode() == parent_id, "--parent-lib-copy must be the same build"
+        builds["parent, second load"] = (lib, h, events(lib))
+    stream = vp(torch.cuda.current_stream(0).cuda_stream)
+    P = 8 << 20
+    mag = ctx.synth_words(61, 2 * P).reshape(P, 2, 16).contiguous()
+    neg = (ctx.synth_words(62, (2 * P + 15) // 16).reshape(-1)[:2 * P] & 1).reshape(P, 2).contiguous()
+    cap = int(L.amph_exchange_max_chars(P))
+    text = {k: torch.zeros(cap, dtype=torch.uint8, device="cuda") for k in builds}
+    ln = {k: torch.zeros(1, dtype=torch.int64, device="cuda") for k in builds}
+    om, on = torch.zeros_like(mag), torch.zeros_like(neg)
+    bad = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def timed(which, fn):
+        lib, h, (e0, e1) = builds[which]
+        lib.amph_time_next_launch(e0, e1)
+        assert fn(lib, h) == 0, lib.amph_last_error()
+        torch.cuda.synchronize()
+        ms = C.c_float()
+        assert lib.amph_timing_event_elapsed_ms(e0, e1, C.byref(ms)) == 0
+        return ms.value
+
+    def enc(which):
+        return timed(which, lambda lib, h: lib.amph_exchange_encode(
+            h, mag.data_ptr(), neg.data_ptr(), P, text[which].data_ptr(), cap, ln[which].data_ptr(),
+            _lib.AMPH_F_DEVICE, stream))
+
+    for k in builds:
+        enc(k)
+    n = int(ln["this tree"].item())
+    for k in builds:
+        assert int(ln[k].item()) == n and torch.equal(text[k][:n], text["this tree"][:n]), k
+
+    def dec(which):
+        return timed(which, lambda lib, h: lib.amph_exchange_decode(
+            h, text["this tree"].data_ptr(), n, P, om.data_ptr(), on.data_ptr(), C.cast(vp(bad.data_ptr()), i64p),
+            _lib.AMPH_F_DEVICE, stream))
+
+    order = ["parent a", "this tree", "parent a2"] + (["parent, second load"] if a.parent_lib_copy else [])
+    build_of = {"parent a": "parent", "parent a2": "parent"}
+    ts = {"%s %s" % (op, k): [] for op in ("encode", "decode") for k in order}
+    for r in range(a.reps + a.warmup):
+        rot = r % len(order)
+        for op, fn in (("encode", enc), ("decode", dec)):
+            for k in order[rot:] + order[:rot]:
+                t = fn(build_of.get(k, k))
+                if r >= a.warmup:
+                    ts["%s %s" % (op, k)].append(t)
+    assert torch.equal(om, mag) and int(bad.item()) == 0x7F7F7F7F7F7F7F7F
+    result = {"tool": "bench_batch --exchange-single", "pairs": P, "text_chars": n, "reps": a.reps,
+              "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "board": board_identity(),
+              "parent_build_id": parent_id, "build_id": _lib.check_build_id(),
+              "timing": "kernel dispatch events, first launch of the call to its last",
+              "rows": {k: stats(v) for k, v in ts.items()}}
+    for op in ("encode", "decode"):
+        base = result["rows"]["%s parent a" % op]["median_ms"]
+        result["%s_us" % op] = {"%s minus parent a" % k: round(
+            1e3 * (result["rows"]["%s %s" % (op, k)]["median_ms"] - base), 3) for k in order[1:]}
+    emit(result)
+
+
+if a.exchange_single:
+    exchange_single_mode()
+    del ctx  # (destroyed while the library is still loaded)
+    sys.exit(0)
+
+if a.exchange:
+    exchange_mode()
+    del ctx  # (destroyed while the library is still loaded)
+    sys.exit(0)
 
 if a.respond:
     respond_mode()
