@@ -164,6 +164,25 @@ def _load():
     L.amph_exchange_decode_packed.argtypes = [vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp, u32, vp]
     L.amph_exchange_encode_batch.argtypes = [vp, pp, pp, C.POINTER(sz), sz, pp, C.POINTER(sz), vp, u32]
     L.amph_exchange_decode_batch.argtypes = [vp, pp, C.POINTER(sz), C.POINTER(sz), sz, pp, pp, i64p, u32]
+    # include/amphora_party_batch.h
+    L.amph_parties_begin.argtypes = [vp, vp, sz, vp, vp, vp, sz, i32, vp, vp, vp, pp]
+    L.amph_parties_begin_dev.argtypes = [vp, vp, sz, vp, vp, vp, sz, i32, vp, vp, vp, vp, pp]
+    for f in (L.amph_parties_objects, L.amph_parties_words, L.amph_parties_text_bytes, L.amph_parties_field_chars):
+        f.restype = sz
+        f.argtypes = [vp]
+    L.amph_parties_text_offsets.argtypes = [vp, vp]
+    L.amph_parties_field_offsets.argtypes = [vp, vp]
+    L.amph_parties_text_lens.argtypes = [vp, vp]
+    L.amph_parties_text.argtypes = [vp, sz, vp, sz]
+    L.amph_parties_text_dev.argtypes = [vp, pp, pp, pp]
+    L.amph_parties_partner.argtypes = [vp, i32, vp, vp, vp]
+    L.amph_parties_partner_dev.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.amph_parties_reset_partner.argtypes = [vp, i32]
+    L.amph_parties_finish.argtypes = [vp, i32, vp, vp]
+    L.amph_parties_finish_b64.argtypes = [vp, i32, pp, vp]
+    L.amph_parties_finish_b64_dev.argtypes = [vp, i32, pp, vp]
+    L.amph_parties_free.restype = None
+    L.amph_parties_free.argtypes = [vp]
     return L
 
 
@@ -228,6 +247,14 @@ EXPORTED_EXCHANGE_BATCH = ["amph_exchange_slot_chars", "amph_exchange_encode_pac
                            "amph_exchange_decode_packed", "amph_exchange_decode_batch",
                            "amph_exchange_batch_copies"]
 AMPH_EXCHANGE_SLOT_ALIGN = 8192
+# what include/amphora_party_batch.h declares
+EXPORTED_PARTY_BATCH = ["amph_parties_begin", "amph_parties_begin_dev", "amph_parties_objects", "amph_parties_words",
+                        "amph_parties_text_bytes", "amph_parties_field_chars", "amph_parties_text_offsets",
+                        "amph_parties_field_offsets", "amph_parties_text_lens", "amph_parties_text",
+                        "amph_parties_text_dev", "amph_parties_partner", "amph_parties_partner_dev",
+                        "amph_parties_reset_partner", "amph_parties_finish", "amph_parties_finish_b64",
+                        "amph_parties_finish_b64_dev", "amph_parties_free"]
+AMPH_PARTIES_ALL = (1 << (8 * C.sizeof(C.c_size_t))) - 1
 ODO_FIELD_NAMES = ("secretShares", "rShares", "vShares", "wShares", "uShares")
 
 
@@ -1429,6 +1456,49 @@ class Context:
                                              C.byref(h)))
         return PartySessionDev(self, h, W, n_parties, yrv, (share_data, masks32, triples96))
 
+    # -- many requests of one party in one device-resident session -------------
+    def parties_begin(self, share_data, share_stride: int, masks32, triples96, word_offsets, n_parties: int,
+                      want_yrv: bool = True) -> "PartySessions":
+        """amph_parties_begin from host buffers: the packed tuples of K
+        requests (request o = words [word_offsets[o], word_offsets[o + 1])) in,
+        the packed (y, r, v) out (unless want_yrv is False), this party's K
+        interimValues texts kept on the device (PartySessions.texts())."""
+        wo = np.ascontiguousarray(word_offsets, dtype=np.uint64)
+        _need(wo.ndim == 1 and wo.size >= 1, "word_offsets: one entry per object and the total")
+        sd = words_view(share_data, share_stride)
+        mk, tr = words_view(masks32, 32), words_view(triples96, 96)
+        T = sd.shape[0]
+        _need(int(wo[-1]) == T, "word_offsets must end at the %d words of the share data" % T)
+        _need(mk.shape[0] == 2 * T, "expected %d input-mask tuples, got %d" % (2 * T, mk.shape[0]))
+        _need(tr.shape[0] == 2 * T, "expected %d multiplication triples, got %d" % (2 * T, tr.shape[0]))
+        yrv = tuple(np.empty((T, 16), np.uint8) for _ in range(3)) if want_yrv else (None, None, None)
+        h = C.c_void_p()
+        self._check(lib.amph_parties_begin(self._h, _ptr(sd), share_stride, _ptr(mk), _ptr(tr), _ptr(wo),
+                                           wo.size - 1, n_parties, *[_ptr(x) for x in yrv], C.byref(h)))
+        return PartySessions(self, h, wo, n_parties, yrv)
+
+    def parties_begin_dev(self, share_data, share_stride: int, masks32, triples96, word_offsets, n_parties: int,
+                          want_yrv: bool = False) -> "PartySessionsDev":
+        """amph_parties_begin_dev on torch device tensors (used in place; the
+        triples must stay unchanged until finish); word_offsets is a host
+        array.  Asynchronous on torch's current stream."""
+        import torch
+        wo = np.ascontiguousarray(word_offsets, dtype=np.uint64)
+        _need(wo.ndim == 1 and wo.size >= 1, "word_offsets: one entry per object and the total")
+        T = int(wo[-1])
+        _need(share_data.is_cuda and masks32.is_cuda and triples96.is_cuda, "device tensors expected")
+        _need(share_data.numel() == T * share_stride, "share data: %d words of %d bytes" % (T, share_stride))
+        _need(masks32.numel() == 64 * T, "expected %d input-mask tuples" % (2 * T))
+        _need(triples96.numel() == 192 * T, "expected %d multiplication triples" % (2 * T))
+        yrv = tuple(torch.empty((T, 16), dtype=torch.uint8, device=share_data.device) for _ in range(3)) \
+            if want_yrv else (None, None, None)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        h = C.c_void_p()
+        self._check(lib.amph_parties_begin_dev(self._h, _ptr(share_data), share_stride, _ptr(masks32),
+                                               _ptr(triples96), _ptr(wo), wo.size - 1, n_parties,
+                                               *[_ptr(x) for x in yrv], stream, C.byref(h)))
+        return PartySessionsDev(self, h, wo, n_parties, yrv, (share_data, masks32, triples96))
+
     # -- synthetic device inputs (bench / tests) --------------------------------
     def synth_odos(self, seed: int, n: int, words: int, fault_index: int = -1,
                    noncanon_permille: int = 0, with_plain: bool = False, buf=None):
@@ -1582,3 +1652,178 @@ class PartySessionDev(PartySession):
         Context._check(lib.amph_party_finish_b64_dev(self._h, int(is_player0), arr, self._stream()))
         return [_dev_view(arr[k], nc, "|u1", self.ctx.device) if nc else None for k in range(5)]
 
+
+
+class PartySessions:
+    """One amph_parties (include/amphora_party_batch.h): K Output Delivery
+    requests of one party, device-resident from the packed tuples to the K
+    responses' base64 fields.  Object o's interimValues text lies at
+    text_offsets[o] of one buffer of text_bytes characters (every party of the
+    exchange has the same layout), its field texts at field_offsets[o] of five
+    buffers of field_chars characters."""
+
+    def __init__(self, ctx: Context, h, word_offsets, n_parties: int, yrv):
+        self.ctx, self._h, self.n = ctx, h, n_parties
+        self.word_offsets = word_offsets
+        self.objects, self.words = int(word_offsets.size - 1), int(word_offsets[-1])
+        self.y, self.r, self.v = yrv
+        self.text_bytes = int(lib.amph_parties_text_bytes(h))
+        self.field_chars = int(lib.amph_parties_field_chars(h))
+        self.text_offsets = np.empty(self.objects, np.uint64)
+        self.field_offsets = np.empty(self.objects, np.uint64)
+        Context._check(lib.amph_parties_text_offsets(h, _ptr(self.text_offsets)))
+        Context._check(lib.amph_parties_field_offsets(h, _ptr(self.field_offsets)))
+
+    def field_lens(self):
+        return [wire_text_chars(int(self.word_offsets[o + 1] - self.word_offsets[o])) for o in range(self.objects)]
+
+    def text_lens(self):
+        out = np.empty(self.objects, np.uint64)
+        Context._check(lib.amph_parties_text_lens(self._h, _ptr(out)))
+        return out
+
+    def text_buffer(self):
+        """-> (the whole text buffer as a uint8 array, the K text lengths)."""
+        out = np.empty(max(self.text_bytes, 1), np.uint8)
+        Context._check(lib.amph_parties_text(self._h, AMPH_PARTIES_ALL, _ptr(out), self.text_bytes))
+        return out[:self.text_bytes], self.text_lens()
+
+    def text(self, o: int) -> bytes:
+        """Object o's interimValues text (the FactorPair JSON array)."""
+        n = int(self.text_lens()[o])
+        out = np.empty(max(n, 1), np.uint8)
+        Context._check(lib.amph_parties_text(self._h, o, _ptr(out), n))
+        return out[:n].tobytes()
+
+    def texts(self):
+        buf, lens = self.text_buffer()
+        return [buf[int(a):int(a) + int(n)].tobytes() for a, n in zip(self.text_offsets, lens)]
+
+    def pack_texts(self, texts):
+        """K texts (bytes) -> (one buffer at the session's offsets, their lengths)."""
+        _need(len(texts) == self.objects, "expected %d texts, got %d" % (self.objects, len(texts)))
+        buf, lens = np.zeros(max(self.text_bytes, 1), np.uint8), np.zeros(self.objects, np.uint64)
+        for o, t in enumerate(texts):
+            if isinstance(t, str):
+                t = t.encode("utf-8")
+            at = int(self.text_offsets[o])
+            room = (int(self.text_offsets[o + 1]) if o + 1 < self.objects else self.text_bytes) - at
+            lens[o] = len(t)
+            if len(t) <= room:  # (a longer one is refused by the call, by its length)
+                buf[at:at + len(t)] = np.frombuffer(bytes(t), np.uint8)
+        return buf[:self.text_bytes], lens
+
+    def partner(self, slot: int, texts, text_lens=None, status: bool = False):
+        """One partner's K texts into slot 1..n-1: a list of K texts, or one
+        buffer at the session's offsets with its lengths.  -> the K verdicts
+        (int64: -1 clean, else the offending offset / the length on a count
+        mismatch); raises ValueError when any text was refused unless status
+        (then -> (verdicts, status))."""
+        if text_lens is None:
+            texts, text_lens = self.pack_texts(texts)
+        buf = np.ascontiguousarray(texts, dtype=np.uint8)
+        lens = np.ascontiguousarray(text_lens, dtype=np.uint64)
+        _need(lens.size == self.objects, "one text length per object")
+        _need(buf.size >= self.text_bytes, "the text buffer holds %d characters" % self.text_bytes)
+        bad = np.full(self.objects, -1, np.int64)
+        st = lib.amph_parties_partner(self._h, slot, _ptr(buf) if buf.size else None, _ptr(lens), _ptr(bad))
+        if st in (AMPH_E_PARAM, AMPH_E_LEN) and (bad >= 0).any():
+            if status:
+                return bad, st
+            raise ValueError(lib.amph_last_error().decode())
+        Context._check(st)
+        return (bad, st) if status else bad
+
+    def reset_partner(self, slot: int):
+        Context._check(lib.amph_parties_reset_partner(self._h, slot))
+
+    def finish(self, is_player0: bool):
+        """-> the packed (w, u) as (T, 16) words."""
+        w, u = np.empty((self.words, 16), np.uint8), np.empty((self.words, 16), np.uint8)
+        Context._check(lib.amph_parties_finish(self._h, int(is_player0), _ptr(w), _ptr(u)))
+        return w, u
+
+    def finish_b64(self, is_player0: bool):
+        """-> (the five slotted field buffers as uint8 arrays of field_chars
+        characters, rejected: K bytes 0 / 1)."""
+        outs = [np.empty(max(self.field_chars, 1), np.uint8) for _ in range(5)]
+        rej = np.zeros(self.objects, np.uint8)
+        arr = (C.c_void_p * 5)(*[_ptr(o) for o in outs])
+        Context._check(lib.amph_parties_finish_b64(self._h, int(is_player0), arr, _ptr(rej)))
+        return [o[:self.field_chars] for o in outs], rej
+
+    def split_fields(self, fields):
+        """The slotted buffers of finish_b64 -> per object the five texts (bytes)."""
+        fl = self.field_lens()
+        return [[bytes(f[int(a):int(a) + n]) for f in fields] for a, n in zip(self.field_offsets, fl)]
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib.amph_parties_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        if lib is not None:
+            self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class PartySessionsDev(PartySessions):
+    """A device-mode amph_parties (amph_parties_*_dev): torch device tensors
+    in and out, every call asynchronous on torch's current stream; close() is
+    the one call that waits."""
+
+    def __init__(self, ctx: Context, h, word_offsets, n_parties: int, yrv, keep):
+        super().__init__(ctx, h, word_offsets, n_parties, yrv)
+        self._keep = keep  # the tuples, read in place until finish
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.ctx.device).cuda_stream)
+
+    def text_dev(self):
+        """-> (the text buffer: uint8 (text_bytes,), its offsets: int64 (K,),
+        the lengths: int64 (K,)), device tensors viewing session memory."""
+        t, o, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        Context._check(lib.amph_parties_text_dev(self._h, C.byref(t), C.byref(o), C.byref(n)))
+        d = self.ctx.device
+        return (_dev_view(t.value, self.text_bytes, "|u1", d), _dev_view(o.value, self.objects, "<i8", d),
+                _dev_view(n.value, self.objects, "<i8", d))
+
+    def text_lens(self):
+        return self.text_dev()[2].cpu().numpy().astype(np.uint64)
+
+    def text_buffer(self):
+        """Synchronises and copies the buffer and the lengths to the host (tests)."""
+        t, _, n = self.text_dev()
+        return t.cpu().numpy(), n.cpu().numpy().astype(np.uint64)
+
+    def text(self, o: int) -> bytes:
+        return self.texts()[o]
+
+    def partner(self, slot: int, texts, text_lens, bad=None):
+        """A partner's text buffer and lengths (device tensors, e.g. its
+        text_dev()) into slot 1..n-1; bad: an int64 (K,) device tensor the
+        decode reports into (returned)."""
+        import torch
+        if bad is None:
+            bad = torch.empty(self.objects, dtype=torch.int64, device=texts.device)
+        Context._check(lib.amph_parties_partner_dev(self._h, slot, _ptr(texts), _ptr(text_lens), _ptr(bad),
+                                                    self._stream()))
+        return bad
+
+    def finish(self, is_player0: bool):
+        raise AmphoraNativeError(AMPH_E_PARAM, "a device-mode session finishes with finish_b64")
+
+    def finish_b64(self, is_player0: bool):
+        """-> the five slotted field buffers: uint8 device tensors viewing the
+        session's memory (valid until close)."""
+        arr = (C.c_void_p * 5)()
+        Context._check(lib.amph_parties_finish_b64_dev(self._h, int(is_player0), arr, self._stream()))
+        return [_dev_view(arr[k], self.field_chars, "|u1", self.ctx.device) if self.field_chars else None
+                for k in range(5)]

@@ -1,12 +1,12 @@
 // Internals shared by the units of the C ABI (capi_*.hip -- capi_ctx,
-// capi_pipeline, capi_words, capi_text, capi_party and capi_batch, the
-// many-objects-per-call families): the context, the error and device
+// capi_pipeline, capi_words, capi_text, capi_party, parties_session and
+// capi_batch, the many-objects-per-call families): the context, the error and device
 // helpers, the word-array pipeline's types and the buffers of one-shot host
 // calls.  Everything here lives in one namespace of hidden
 // visibility: the library exports only what include/amphora.h and its
 // extension headers include/amphora_wire_batch.h,
-// include/amphora_upload_batch.h, include/amphora_respond_batch.h and
-// include/amphora_exchange_batch.h declare.
+// include/amphora_upload_batch.h, include/amphora_respond_batch.h,
+// include/amphora_exchange_batch.h and include/amphora_party_batch.h declare.
 //
 // Host-pointer calls stream the word arrays through the device in batches
 // (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
@@ -37,6 +37,7 @@
 #include "../../include/amphora_upload_batch.h"
 #include "../../include/amphora_respond_batch.h"
 #include "../../include/amphora_exchange_batch.h"
+#include "../../include/amphora_party_batch.h"
 #include "host_stream.hpp"
 #include "kernels.hpp"
 
@@ -177,6 +178,15 @@ namespace capi __attribute__((visibility("hidden"))) {
 // once more when memory runs out (capi_ctx.hip)
 size_t pool_bytes(const amph_ctx* c);
 hipError_t dev_ensure(amph_ctx* c, DevBuf& b, size_t bytes);
+// the party sessions' buffers (capi_party.hip; c->mu held): pool_put hands one
+// back to the context's pool -- at most kPartyPoolMax buffers and
+// c->pool_cap_bytes bytes, the smallest dropped first; pool_ensure makes b
+// hold at least `bytes`: kept, or the best-fitting pooled buffer, or a new
+// allocation (after freeing the pool if memory ran out)
+constexpr size_t kPartyPoolMax = 16;
+void pool_put(amph_ctx* c, DevBuf& b);
+hipError_t pool_ensure(amph_ctx* c, DevBuf& b, size_t bytes);
+inline size_t b64_chars(size_t nbytes) { return 4 * ((nbytes + 2) / 3); }
 u128 mulmod_host(const amph_ctx* c, u128 a, u128 b);  // a < p
 amph::LaunchCfg cfg(amph_ctx* c, hipStream_t s, size_t words);
 inline int check_ctx(amph_ctx* c) { return c ? AMPH_OK : fail(AMPH_E_PARAM, "null context"); }

@@ -51,13 +51,8 @@ struct amph_party {
   }
 };
 
-namespace {
-size_t b64_chars(size_t nbytes) { return 4 * ((nbytes + 2) / 3); }
-
-constexpr size_t kPartyPoolMax = 16;
-
-// (c->mu held) hand a session buffer back to the context's pool: at most
-// kPartyPoolMax buffers and c->pool_cap_bytes bytes, the smallest dropped first
+namespace capi __attribute__((visibility("hidden"))) {
+// (declared in capi_internal.hpp: parties_session.hip shares them)
 void pool_put(amph_ctx* c, DevBuf& b) {
   if (!b.p) return;
   c->party_pool.push_back(b);
@@ -73,8 +68,6 @@ void pool_put(amph_ctx* c, DevBuf& b) {
   }
 }
 
-// (c->mu held) b holds at least `bytes`: kept, or the best-fitting pooled
-// buffer, or a new allocation (after freeing the pool if memory ran out)
 hipError_t pool_ensure(amph_ctx* c, DevBuf& b, size_t bytes) {
   if (bytes <= b.cap) return hipSuccess;
   pool_put(c, b);
@@ -89,7 +82,9 @@ hipError_t pool_ensure(amph_ctx* c, DevBuf& b, size_t bytes) {
   }
   return dev_ensure(c, b, bytes);
 }
+}  // namespace capi
 
+namespace {
 int party_check(amph_party* p) {
   if (!p || !p->c) return fail(AMPH_E_PARAM, "null party session");
   if (p->finished) return fail(AMPH_E_PARAM, "the party session is already finished");

@@ -34,6 +34,7 @@
 #include "kernels.hpp"
 #include "decimal.hpp"
 #include "exchangetiles.hpp"
+#include "partytiles.hpp"
 
 namespace amph {
 
@@ -1219,17 +1220,20 @@ __global__ __launch_bounds__(kDecBlock) void k_xdec_fast(Text text, const uint64
 // span-0 value that opens it; the scan of these words gives every span its
 // first value index (and the map k_open_post starts from), and any kWsBit sends
 // the whole text through k_xdec_slow, which writes pair order instead.
-__global__ __launch_bounds__(kDecBlock) void k_xdec_span(Text text, uint64_t* cnt, uint4* smag,
-                                                     uint8_t* sneg, unsigned long long* bad) {
-  // (the passes after this one report into *bad; null: the caller has reset it)
-  if (bad && blockIdx.x == 0 && threadIdx.x == 0) *bad = kNoFail;
+//
+// One span of it, by one workgroup: span `span` of `text`, its values stored
+// at the slots of span `out` and its count word at cnt[out] (k_xdec_span:
+// out = span; k_xdecs_span: `span` counts inside the object's own text, `out`
+// in the buffer).
+__device__ __forceinline__ void xdec_span_body(const Text& text, size_t span, size_t out, uint64_t* cnt, uint4* smag,
+                                               uint8_t* sneg) {
   __shared__ uint4 win4[kWin / 16 + 1];
   __shared__ uint16_t pos[kXSpanSlots];  // colon, relative to b0
   __shared__ uint32_t p10[8];  // 10^k, k < 8: the partial chunk's scale (one LDS read per value)
   __shared__ int sfail;
   if (threadIdx.x == 0) sfail = 0;
   if (threadIdx.x < 8) p10[threadIdx.x] = pow10_small(threadIdx.x);
-  const size_t span = blockIdx.x, b0 = span * kDecSpan;
+  const size_t b0 = span * kDecSpan;
   const long long w0 = (long long)b0 - kWinPad;
   if (w0 >= (long long)text.mis && w0 + 16LL * (kWin / 16 + 1) <= (long long)text.L) {
     const u32x4* a = reinterpret_cast<const u32x4*>(text.al + w0);
@@ -1261,8 +1265,8 @@ __global__ __launch_bounds__(kDecBlock) void k_xdec_span(Text text, uint64_t* cn
   bool fail = total > (uint32_t)kXSpanSlots || (span == 0 && total == 0 && len > 0);
   const uint32_t nloc = min(total, (uint32_t)kXSpanSlots);
   const uint32_t* l32 = reinterpret_cast<const uint32_t*>(win4);
-  uint4* dst = smag + span * kXSpanSlots;
-  uint8_t* dneg = sneg + span * kXSpanSlots;
+  uint4* dst = smag + out * kXSpanSlots;
+  uint8_t* dneg = sneg + out * kXSpanSlots;
   for (uint32_t idx = threadIdx.x; idx < nloc; idx += kDecBlock) {
     const uint32_t at = pos[idx];
     FastNum fn;
@@ -1276,7 +1280,14 @@ __global__ __launch_bounds__(kDecBlock) void k_xdec_span(Text text, uint64_t* cn
   }
   if (__ballot(fail) != 0 && __lane_id() == 0) sfail = 1;  // (__syncthreads_or costs 4 KiB of LDS)
   __syncthreads();
-  if (threadIdx.x == 0) cnt[span] = total | (sfail ? kWsBit : 0);
+  if (threadIdx.x == 0) cnt[out] = total | (sfail ? kWsBit : 0);
+}
+
+__global__ __launch_bounds__(kDecBlock) void k_xdec_span(Text text, uint64_t* cnt, uint4* smag,
+                                                     uint8_t* sneg, unsigned long long* bad) {
+  // (the passes after this one report into *bad; null: the caller has reset it)
+  if (bad && blockIdx.x == 0 && threadIdx.x == 0) *bad = kNoFail;
+  xdec_span_body(text, blockIdx.x, blockIdx.x, cnt, smag, sneg);
 }
 
 // ---- many objects per call (include/amphora_exchange_batch.h) ------------------------
@@ -1537,6 +1548,63 @@ __global__ __launch_bounds__(kDecBlock) void k_xdecs_slow(XDecTables a, const ui
   }
 }
 
+// ---- many objects' span form (include/amphora_party_batch.h; partytiles.hpp) ---------
+// k_xdec_span over K texts in one read: the workgroup of buffer span s parses
+// the span of its own object's text (xdec_span: offsets, length and the
+// first-value rule inside that text) into the slots of span s; a span in no
+// text counts 0 and reads nothing.  The workgroup of an object's first span
+// resets its verdict word.  After ONE scan of the count words over the grid,
+// object o is in span form iff bscan[span0 + spans] - bscan[span0] == 2 P_o
+// exactly: no fail bit among its spans, and the right count.
+// (amdgpu_num_sgpr: left alone the lookup took 100 SGPRs, and 256-thread
+// workgroups above 96 are admitted six per CU instead of eight; at 80 the
+// compiler reports 78 with no spill and k_xdec_span's 43 VGPRs.)
+static_assert(kXSpanSlots == (int)kPartySpanSlots, "partytiles.hpp states the span form's slot stride");
+__global__ __launch_bounds__(kDecBlock) __attribute__((amdgpu_num_sgpr(80))) void k_xdecs_span(XDecTables a, uint64_t* cnt, uint4* smag, uint8_t* sneg,
+                                                      unsigned long long* bad) {
+  const XDecSpan d = a.span(blockIdx.x);
+  if (!d.owns) {  // (the whole workgroup)
+    if (threadIdx.x == 0) cnt[blockIdx.x] = 0;
+    return;
+  }
+  if (d.local == 0 && threadIdx.x == 0) bad[d.object] = kNoFail;
+  xdec_span_body(a.text(d), d.local, blockIdx.x, cnt, smag, sneg);
+}
+
+// The pass after the scan, k_xdec_slow<SpanBases> per object: the array check
+// (the workgroup of the object's first span); for an object in span form the
+// windows of its open-post tiles (partytiles.hpp), shared among the
+// workgroups of its spans; for any other object the general pass over its own
+// spans, into ITS rows of the pair-order arrays, and the pair-order mark in
+// its tiles' windows.  A tile's window lies at its workgroup's index in the
+// open-post grid, so k_open_post_seg learns form and place from one load.
+__global__ __launch_bounds__(kDecBlock) void k_xdecs_post(XDecTables a, const uint64_t* bscan, size_t nb, uint4* pmag,
+                                                      uint8_t* pneg, uint4* win, unsigned long long* bad) {
+  for (size_t span = blockIdx.x; span < nb; span += gridDim.x) {
+    const XDecSpan d = a.span(span);
+    if (!d.owns) continue;
+    const Text text = a.text(d);
+    const uint64_t* base = bscan + d.span0;  // d.span0 + d.spans <= nb
+    const uint64_t tot = base[d.spans] - base[0];  // the object's values, fail bits above kCountMask
+    const bool span_form = tot == d.nvals;
+    if (d.local == 0) {
+      array_check(text, tot & kCountMask, (size_t)d.nvals, bad + d.object);
+      __syncthreads();  // (its LDS words, before the next object's)
+    }
+    const uint64_t pairs = d.nvals / 2;
+    const size_t g = (size_t)(d.row0 / 2 / kPartyTilePairs) + d.object;  // party_tile's base_tile
+    const size_t tiles = (size_t)((pairs + kPartyTilePairs - 1) / kPartyTilePairs);
+    for (size_t t = d.local * kDecBlock + threadIdx.x; t < tiles; t += d.spans * kDecBlock) {
+      PartyWindow w{kPartyPairOrder, 0, 0, 0};
+      if (span_form) w = party_window(base, d.spans, t);
+      win[g + t] = make_uint4(w.x, w.y, w.z, w.w);
+    }
+    if (span_form) continue;
+    xdec_general_span(text, d.local, (bscan[span] - base[0]) & kCountMask, (size_t)d.nvals, pmag + d.row0,
+                      pneg + d.row0, bad + d.object);
+  }
+}
+
 unsigned blocks_of(size_t n, size_t per) { return (unsigned)((n + per - 1) / per); }
 
 // exclusive scan of x[0..n) in place, x[n] = total; bsum: blocks_of(n)+1 scratch
@@ -1750,6 +1818,33 @@ hipError_t launch_exchange_decode_spans(const char* text, size_t len, size_t npa
   AMPH_LAUNCH(k_xdec_slow<SpanBases>, dim3((unsigned)std::min<size_t>(nb, kSlowGrid)), dim3(kDecBlock), c1, t,
               (SpanBases{out.base, nb, 2 * npairs, out.map}), nb, 2 * npairs, out.mag, out.neg, bad,
               (const unsigned int*)nullptr);
+  return hipGetLastError();
+}
+
+size_t xspans_seg_scratch_bytes(size_t texts_len) {
+  return 8 * ((size_t)blocks_of(xdec_span_grid(texts_len), kScanBlock) + 1);
+}
+
+// the span pass over the whole buffer (which also resets bad), the scan of
+// its count words (two launches whatever the grid is), the checks, windows
+// and general pass: four launches whatever n_objects is
+hipError_t launch_exchange_decode_spans_seg(const char* texts, size_t texts_len, const uint64_t* pair_offsets,
+                                            const uint64_t* text_offsets, const uint64_t* text_lens,
+                                            size_t n_objects, size_t npairs, const XSpansSeg& out,
+                                            unsigned long long* bad, void* scratch, const LaunchCfg& c) {
+  const size_t nb = xdec_span_grid(texts_len);
+  if (n_objects == 0 || nb > 0x7FFFFFFFu || out.nb != nb) return hipErrorInvalidValue;
+  const XDecTables a{reinterpret_cast<const uint8_t*>(texts), text_offsets, text_lens, pair_offsets, n_objects,
+                     (uint64_t)npairs, (uint64_t)texts_len};
+  LaunchCfg c0 = c, cm = c, c1 = c;
+  c0.ev_stop = nullptr;
+  cm.ev_start = cm.ev_stop = nullptr;
+  c1.ev_start = nullptr;
+  AMPH_LAUNCH(k_xdecs_span, dim3((unsigned)nb), dim3(kDecBlock), c0, a, out.base, out.mag, out.neg, bad);
+  hipError_t e = scan_u64_fixed(out.base, nb, static_cast<uint64_t*>(scratch), cm);
+  if (e != hipSuccess) return e;
+  AMPH_LAUNCH(k_xdecs_post, dim3((unsigned)std::min<size_t>(nb, kSlowGrid)), dim3(kDecBlock), c1, a,
+              (const uint64_t*)out.base, nb, out.pmag, out.pneg, out.win, bad);
   return hipGetLastError();
 }
 

@@ -24,6 +24,7 @@
 #include "decimal.hpp"
 #include "devio.hpp"
 #include "wiretiles.hpp"
+#include "partytiles.hpp"
 
 namespace amph {
 
@@ -613,15 +614,42 @@ __device__ __forceinline__ size_t span_slot(const SpanWin& w, const uint64_t* ba
   return s * kXSpanSlots + (v - base[s]);
 }
 
-__device__ __forceinline__ void span_pair(const uint4* mag, const uint8_t* negb, const uint64_t* base, size_t nb,
-                                          const SpanWin& w, size_t k, uint4& md, uint4& me, uint32_t& sg) {
-  const size_t a = span_slot(w, base, nb, 2 * k), b = span_slot(w, base, nb, 2 * k + 1);
+// a pair's two values from slots a, b of a decoded text (byte: sign | key "b" << 1)
+__device__ __forceinline__ void span_pair_at(const uint4* mag, const uint8_t* negb, size_t a, size_t b, uint4& md,
+                                             uint4& me, uint32_t& sg) {
   const uint4 x = ld(mag + a), y = ld(mag + b);
   const uint32_t nx = negb[a], ny = negb[b];
   const bool swap = (nx & 2u) != 0;
   md = swap ? y : x;
   me = swap ? x : y;
   sg = swap ? ((ny & 1u) | ((nx & 1u) << 8)) : ((nx & 1u) | ((ny & 1u) << 8));
+}
+
+__device__ __forceinline__ void span_pair(const uint4* mag, const uint8_t* negb, const uint64_t* base, size_t nb,
+                                          const SpanWin& w, size_t k, uint4& md, uint4& me, uint32_t& sg) {
+  span_pair_at(mag, negb, span_slot(w, base, nb, 2 * k), span_slot(w, base, nb, 2 * k + 1), md, me, sg);
+}
+
+// The arithmetic of the fused open + product step, shared by k_open_post and
+// k_open_post_seg: one party's signed diff pair into the running D, E ...
+template <bool BIG>
+__device__ __forceinline__ void open_acc(W4& D, W4& E, const uint4& md, const uint4& me, uint32_t sg, const Fp& f) {
+  const W4 x = canon<BIG>(w4(md), f), y = canon<BIG>(w4(me), f);
+  D = (sg & 0xFF) ? mod_sub(D, x, f) : mod_add(D, x, f);
+  E = (sg >> 8) ? mod_sub(E, y, f) : mod_add(E, y, f);
+}
+
+// ... and K_ODO_POST on the opened (canonical) D, E of pair k, its triple in
+// the lane's staged slots
+template <bool BIG>
+__device__ __forceinline__ void post_store(const uint4* tri, const W4& D, const W4& E, int p0, size_t k, uint4* ow,
+                                           uint4* ou, const Fp& f) {
+  const W4 a = w4(tri[threadIdx.x * 7]), b = w4(tri[threadIdx.x * 7 + 2]);
+  const W4 c = w4(tri[threadIdx.x * 7 + 4]);
+  const W4 r2 = r2_word(f);
+  const W4 bb = p0 ? mod_add(canon<BIG>(b, f), mont_mul(E, r2, f), f) : b;
+  const W4 x = dot2_redc(D, bb, E, a, f);
+  st_out((k & 1 ? ou : ow) + (k >> 1), mod_add(canon<BIG>(c, f), mont_mul(x, r2, f), f));
 }
 
 // SPAN: parties 1 .. NP-1 are partners in the span form, party 0 this party's
@@ -678,9 +706,7 @@ __global__ __launch_bounds__(kPairBlock) void k_open_post(SignedSet d, int n, co
         md[j] = lds[kPairBlock * 7 + j * kPairBlock * 3 + 3 * threadIdx.x];
         me[j] = lds[kPairBlock * 7 + j * kPairBlock * 3 + 3 * threadIdx.x + 1];
       }
-      const W4 x = canon<BIG>(w4(md[j]), f), y = canon<BIG>(w4(me[j]), f);
-      D = (sg[j] & 0xFF) ? mod_sub(D, x, f) : mod_add(D, x, f);
-      E = (sg[j] >> 8) ? mod_sub(E, y, f) : mod_add(E, y, f);
+      open_acc<BIG>(D, E, md[j], me[j], sg[j], f);
     }
   } else {
     __syncthreads();
@@ -697,18 +723,107 @@ __global__ __launch_bounds__(kPairBlock) void k_open_post(SignedSet d, int n, co
         mx = ld(d.mag[j] + 2 * k);
         my = ld(d.mag[j] + 2 * k + 1);
       }
-      const W4 x = canon<BIG>(w4(mx), f), y = canon<BIG>(w4(my), f);
-      D = (s & 0xFF) ? mod_sub(D, x, f) : mod_add(D, x, f);
-      E = (s >> 8) ? mod_sub(E, y, f) : mod_add(E, y, f);
+      open_acc<BIG>(D, E, mx, my, s, f);
     }
   }
-  // K_ODO_POST on the opened (canonical) D, E
-  const W4 a = w4(tri[threadIdx.x * 7]), b = w4(tri[threadIdx.x * 7 + 2]);
-  const W4 c = w4(tri[threadIdx.x * 7 + 4]);
-  const W4 r2 = r2_word(f);
-  const W4 bb = p0 ? mod_add(canon<BIG>(b, f), mont_mul(E, r2, f), f) : b;
-  const W4 x = dot2_redc(D, bb, E, a, f);
-  st_out((k & 1 ? ou : ow) + (k >> 1), mod_add(canon<BIG>(c, f), mont_mul(x, r2, f), f));
+  post_store<BIG>(tri, D, E, p0, k, ow, ou, f);
+}
+
+// k_open_post over many objects (launch_open_post_seg; partytiles.hpp): one
+// workgroup per 128-pair tile of ONE object.  Party 0's diffs are pair
+// ordered; a partner's come through the tile's window into the span form of
+// its text, or from its pair-order rows when the window carries the
+// pair-order mark -- one uniform load per partner tells which, issued before
+// the triples are staged (as span_win's).  Slots are counted from the
+// object's first span in the buffer, text_offsets[object] / 8192.  The tile of
+// an object's first pairs also min-combines the partners' verdict words for
+// the object into reject[object], which the response encoder reads next.
+static_assert(kPairBlock == (int)kPartyTilePairs && kXSpanSlots == (int)kPartySpanSlots &&
+                  kXSpanBytes == kXSlotAlign,
+              "partytiles.hpp states this file's tile and the span form's stride");
+struct SegWin {
+  PartyWindow w;
+  const uint64_t* base;  // the scanned counts at the object's first span
+};
+
+__device__ __forceinline__ void seg_pair(const XSpansSeg& x, const SegWin& sw, size_t span0, size_t local, size_t k,
+                                         uint4& md, uint4& me, uint32_t& sg) {
+  if (sw.w.x == kPartyPairOrder) {  // (the whole workgroup)
+    span_pair_at(x.pmag, x.pneg, 2 * k, 2 * k + 1, md, me, sg);
+    return;
+  }
+  const uint32_t q = 2 * threadIdx.x;
+  span_pair_at(x.mag, x.neg, party_slot(sw.w, sw.base, span0, x.nb, local, q),
+               party_slot(sw.w, sw.base, span0, x.nb, local, q + 1), md, me, sg);
+}
+
+template <int NP, bool BIG>
+__global__ __launch_bounds__(kPairBlock) void k_open_post_seg(PartySegSet d, int n, const uint4* triples, int p0,
+                                                             uint4* ow, uint4* ou, Fp f) {
+  __shared__ uint4 tri[kPairBlock * 7];
+  const PartyTile t = party_tile(d.pair_offsets, d.n_objects, d.npairs, blockIdx.x);
+  if (!t.owns) return;  // (the whole workgroup)
+  const size_t nb = d.span[n > 1 ? 1 : 0].nb;
+  const size_t span0 = n > 1 ? (size_t)xseg_min(d.text_offsets[t.object] / kXSpanBytes, nb - 1) : 0;
+  const size_t k = t.pair0 + threadIdx.x;
+  const bool on = threadIdx.x < t.pairs;
+  auto window = [&](int j) {
+    const uint4 e = d.span[j].win[blockIdx.x];
+    return SegWin{PartyWindow{e.x, e.y, e.z, e.w}, d.span[j].base + span0};
+  };
+  SegWin sw[NP > 0 ? NP : 1];
+  if constexpr (NP > 0) {
+#pragma unroll
+    for (int j = 1; j < NP; ++j) sw[j] = window(j);
+  }
+  stage_tuples<6, kPairBlock>(tri, triples + 6 * t.pair0, t.pairs);
+  W4 D = {}, E = {};
+  uint4 m0d = make_uint4(0, 0, 0, 0), m0e = m0d;
+  uint32_t s0 = 0;
+  if (on) {
+    m0d = ld(d.mag0 + 2 * k);
+    m0e = ld(d.mag0 + 2 * k + 1);
+    s0 = reinterpret_cast<const uint16_t*>(d.neg0)[k];
+  }
+  if constexpr (NP > 0) {
+    uint4 md[NP], me[NP];
+    uint32_t sg[NP];
+    md[0] = m0d;
+    me[0] = m0e;
+    sg[0] = s0;
+#pragma unroll
+    for (int j = 1; j < NP; ++j) {
+      md[j] = me[j] = make_uint4(0, 0, 0, 0);
+      sg[j] = 0;
+      if (on) seg_pair(d.span[j], sw[j], span0, t.local, k, md[j], me[j], sg[j]);
+    }
+    if (t.local == 0 && threadIdx.x == 0) {
+      unsigned long long r = kNoFail;
+#pragma unroll
+      for (int j = 1; j < NP; ++j) r = min(r, d.verdict[j][t.object]);
+      d.reject[t.object] = r;
+    }
+    __syncthreads();
+    if (!on) return;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) open_acc<BIG>(D, E, md[j], me[j], sg[j], f);
+  } else {
+    if (t.local == 0 && threadIdx.x == 0) {
+      unsigned long long r = kNoFail;
+      for (int j = 1; j < n; ++j) r = min(r, d.verdict[j][t.object]);
+      d.reject[t.object] = r;
+    }
+    __syncthreads();
+    if (!on) return;
+    open_acc<BIG>(D, E, m0d, m0e, s0, f);
+    for (int j = 1; j < n; ++j) {
+      uint4 mx, my;
+      uint32_t s;
+      seg_pair(d.span[j], window(j), span0, t.local, k, mx, my, s);
+      open_acc<BIG>(D, E, mx, my, s, f);
+    }
+  }
+  post_store<BIG>(tri, D, E, p0, k, ow, ou, f);
 }
 
 // MpSpdzIntegrationUtils.toGfp / fromGfp over arrays, and maskInput with
@@ -1018,6 +1133,20 @@ hipError_t launch_open_post(const SignedSet& d, int n, const uint4* triples, siz
                              pairs, p0, ow, ou, f);                                                      \
   else AMPH_LAUNCH((k_open_post<NP, BIG, false, false>), g, dim3(kPairBlock), c, d, n, triples, pairs,  \
                    p0, ow, ou, f)
+  if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
+#undef L
+  return hipGetLastError();
+}
+
+hipError_t launch_open_post_seg(const PartySegSet& d, int n, const uint4* triples, int p0, uint4* ow, uint4* ou,
+                                const Fp& f, const LaunchCfg& c) {
+  if (n < 1 || n > kMaxParties || d.n_objects == 0) return hipErrorInvalidValue;
+  const size_t grid = party_tile_grid(d.npairs, d.n_objects);
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  for (int j = 2; j < n; ++j)
+    if (d.span[j].nb != d.span[1].nb) return hipErrorInvalidValue;  // one text layout for every partner
+  const dim3 g((unsigned)grid);
+#define L(NP, BIG) AMPH_LAUNCH((k_open_post_seg<NP, BIG>), g, dim3(kPairBlock), c, d, n, triples, p0, ow, ou, f)
   if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP(n, false, L) }
 #undef L
   return hipGetLastError();

@@ -218,6 +218,54 @@ hipError_t launch_exchange_decode_seg(const char* texts, size_t texts_len, const
                                       size_t npairs, uint4* mag, uint8_t* neg, unsigned long long* bad,
                                       bool reset_bad, void* scratch, const LaunchCfg& c);
 
+// Many objects' partner texts in SPAN FORM (include/amphora_party_batch.h;
+// partytiles.hpp): the texts lie at text_offsets[o] of one 16-byte-aligned
+// buffer as above.  mag / neg: kXSpanSlots slots per 8 KiB span of the BUFFER
+// (nb = texts_len / 8192 + 1 spans), the values of buffer span s in text order
+// from slot kXSpanSlots s; base[nb + 1]: the scanned count words.  Object o is
+// in span form iff base[span0 + spans] - base[span0] == 2 P_o; any other
+// object's values are written in pair order into rows [2 pair_offsets[o], ...)
+// of pmag / pneg (2 npairs rows; byte = sign), for that object alone.
+// win[party_tile_grid(npairs, n_objects)]: the window of every open-post
+// tile, x = kPartyPairOrder for a tile of an object in pair order.
+// bad[o]: reset, then object o's verdict as launch_exchange_decode_seg's.
+struct XSpansSeg {
+  uint4* mag;
+  uint8_t* neg;
+  uint64_t* base;
+  uint4* pmag;
+  uint8_t* pneg;
+  uint4* win;
+  size_t nb;
+};
+size_t xspans_seg_scratch_bytes(size_t texts_len);
+hipError_t launch_exchange_decode_spans_seg(const char* texts, size_t texts_len, const uint64_t* pair_offsets,
+                                            const uint64_t* text_offsets, const uint64_t* text_lens,
+                                            size_t n_objects, size_t npairs, const XSpansSeg& out,
+                                            unsigned long long* bad, void* scratch, const LaunchCfg& c);
+
+// launch_open_post over many objects (partytiles.hpp): one workgroup per
+// 128-pair tile that never straddles two objects.  Party 0's diffs are pair
+// ordered (K_ODO_PRE's arrays over the concatenation); parties 1 .. n-1 are
+// partners decoded by launch_exchange_decode_spans_seg (span[j], verdict[j] =
+// the n_objects verdict words of that decode).  w and u are stored at the
+// packed word positions; the tile of an object's first pairs also writes
+// reject[object] = the smallest of the partners' verdict words for it
+// (kNoFail without partners; an object of no pairs keeps no tile and its word
+// is not written).  Tables are device arrays.
+struct PartySegSet {
+  const uint4* mag0;
+  const uint32_t* neg0;
+  XSpansSeg span[kMaxParties];
+  const unsigned long long* verdict[kMaxParties];
+  const uint64_t *pair_offsets, *text_offsets;
+  size_t n_objects;
+  uint64_t npairs;
+  unsigned long long* reject;
+};
+hipError_t launch_open_post_seg(const PartySegSet& d, int n, const uint4* triples, int is_player0, uint4* out_w,
+                                uint4* out_u, const Fp& f, const LaunchCfg& c);
+
 // Synthetic honest n-party ODOs (bench/test input generator, device-side).
 struct OutSet {
   uint4* f[5][kMaxParties];

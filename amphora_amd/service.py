@@ -195,21 +195,27 @@ class OutputDeliveryService:
     exchange_format="session": the same JSON bodies, with the request run as a
     device-resident party session (amph_party_*): the triples and every party's
     diffs stay on the GPU between the open's two halves (needs n_parties).
+    exchange_format="session_batch": the same bodies again, with ALL the live
+    requests of a call run as ONE device-resident batch session
+    (amph_parties_*, include/amphora_party_batch.h): a fixed number of
+    launches whatever the request count, one verdict per request; the
+    single-request functions run a batch of one (needs n_parties).
     """
 
     def __init__(self, ctx: _lib.Context, player_id: int,
                  tuple_source: Callable[[uuid.UUID, str, int], bytes],
                  exchange: Callable, exchange_format: str = "objects", n_parties: int = None):
-        if exchange_format not in ("objects", "json", "session"):
-            raise ValueError("exchange_format must be 'objects', 'json' or 'session'")
-        if exchange_format == "session" and not n_parties:
-            raise ValueError("exchange_format='session' needs n_parties")
+        if exchange_format not in ("objects", "json", "session", "session_batch"):
+            raise ValueError("exchange_format must be 'objects', 'json', 'session' or 'session_batch'")
+        if exchange_format in ("session", "session_batch") and not n_parties:
+            raise ValueError("exchange_format='%s' needs n_parties" % exchange_format)
         self._ctx = ctx
         self.player_id = player_id
         self._tuples = tuple_source
         self._exchange = exchange
         self._json = exchange_format == "json"
         self._session = exchange_format == "session"
+        self._session_batch = exchange_format == "session_batch"
         self.n_parties = n_parties
         self.last_exchange_object = None
 
@@ -316,6 +322,11 @@ class OutputDeliveryService:
         return opened
 
     def _compute(self, share_words, stride, request_id):
+        if self._session_batch:  # a batch of one
+            res = self._compute_many([share_words], stride, [request_id])[0]
+            if isinstance(res, Exception):
+                raise res
+            return res
         W = share_words.shape[0]
         masks = self._download(request_id, INPUT_MASK_GFP, 2 * W)
         op_id = name_uuid_from_bytes(("%s_%d" % (request_id, 2 * W)).encode())  # :140-141
@@ -372,7 +383,9 @@ class OutputDeliveryService:
         partners' bodies parsed by one batch decode (_open_many).  Returns one entry per request: the
         OutputDeliveryObject, or the AmphoraServiceException the single function
         raises for that request (the others are unaffected).
-        exchange_format="session" is one request by construction: a loop."""
+        exchange_format="session" is one request by construction: a loop;
+        "session_batch" runs the live requests as one batch session
+        (_compute_many_session)."""
         if len(shares) != len(request_ids):
             raise ValueError("one request id per share")
         if self._session:
@@ -398,6 +411,8 @@ class OutputDeliveryService:
         live = sorted(got)
         if not live:
             return out
+        if self._session_batch:
+            return self._compute_many_session(words, stride, got, out)
         at, off = 0, {}
         for o in live:
             off[o] = at
@@ -429,6 +444,67 @@ class OutputDeliveryService:
                 out[o] = OutputDeliveryObject(y[a:a + W].tobytes(), r[a:a + W].tobytes(), v[a:a + W].tobytes(),
                                               w[g0:g0 + W].tobytes(), u[g0:g0 + W].tobytes())
                 g0 += W
+        return out
+
+    def _compute_many_session(self, words, stride, got, out) -> list:
+        """_compute_many's live requests (got = {o: (masks, op_id, triples)}) as
+        ONE batch session: begin over the concatenation, the exchange callback
+        per request on wire.exchange_body of its own text, every partner's K
+        texts in one call per slot, one finish.  A request whose exchange
+        fails, whose partner body carries another operation id or count, or
+        whose partner text the decode refuses gets the AmphoraServiceException
+        _compute_session raises for it; its slots are filled with an empty
+        text, which the session rejects for that object alone."""
+        from . import wire
+        live = sorted(got)
+        woff = np.concatenate([[0], np.cumsum([words[o].shape[0] for o in live])]).astype(np.uint64)
+        n, failed = self.n_parties, {}
+        with self._ctx.parties_begin(np.concatenate([words[o] for o in live]), stride,
+                                     np.concatenate([got[o][0] for o in live]),
+                                     np.concatenate([got[o][2] for o in live]), woff, n) as s:
+            texts = [[b""] * len(live) for _ in range(n)]  # texts[slot][k]
+            for k, (o, own_text) in enumerate(zip(live, s.texts())):
+                op_id = got[o][1]
+                own = wire.exchange_body(op_id, self.player_id, own_text)
+                self.last_exchange_object = own
+                try:
+                    partners = self._exchange(own)
+                    if len(partners) != n - 1:
+                        raise ValueError("%d partner bodies, %d expected" % (len(partners), n - 1))
+                    mine = []
+                    for body in partners:
+                        body = bytes(body)
+                        p_op, _, lb, rb = wire.exchange_span(body)
+                        if p_op != op_id:
+                            raise ValueError("operation id %s != %s" % (p_op, op_id))
+                        if rb + 1 - lb > _lib.exchange_slot_chars(2 * words[o].shape[0]):
+                            raise ValueError("interimValues must hold exactly %d FactorPairs"
+                                             % (2 * words[o].shape[0]))  # (longer than any text of that many)
+                        mine.append(body[lb:rb + 1])
+                    for slot, t in enumerate(mine, start=1):
+                        texts[slot][k] = t
+                except Exception as e:  # noqa: BLE001 -- this request's own outcome
+                    failed[o] = e
+            for slot in range(1, n):
+                bad, _ = s.partner(slot, texts[slot], status=True)
+                for k, o in enumerate(live):
+                    if bad[k] >= 0 and o not in failed:
+                        P = 2 * words[o].shape[0]
+                        failed[o] = ValueError("interimValues must hold exactly %d FactorPairs" % P
+                                               if bad[k] == len(texts[slot][k])
+                                               else "Malformed FactorPair JSON at offset %d" % bad[k])
+            w, u = s.finish(self.player_id == 0)
+            for k, o in enumerate(live):
+                a, b = int(woff[k]), int(woff[k + 1])
+                if o in failed:
+                    try:
+                        raise AmphoraServiceException("Failed to open values for operation #%s" % got[o][1]) \
+                            from failed[o]
+                    except AmphoraServiceException as x:
+                        out[o] = x
+                else:
+                    out[o] = OutputDeliveryObject(s.y[a:b].tobytes(), s.r[a:b].tobytes(), s.v[a:b].tobytes(),
+                                                  w[a:b].tobytes(), u[a:b].tobytes())
         return out
 
     def get_input_masks_as_output_delivery_objects(self, request_ids, counts) -> list:
