@@ -183,6 +183,23 @@ def _load():
     L.amph_parties_finish_b64_dev.argtypes = [vp, i32, pp, vp]
     L.amph_parties_free.restype = None
     L.amph_parties_free.argtypes = [vp]
+    # include/amphora_client_session.h
+    L.amph_client_begin.argtypes = [vp, sz, i32, pp]
+    L.amph_client_begin_dev.argtypes = [vp, sz, i32, vp, pp]
+    L.amph_client_party.argtypes = [vp, i32, vp, i64p]
+    L.amph_client_party_dev.argtypes = [vp, i32, vp, i64p, vp]
+    L.amph_client_finish_verify.argtypes = [vp, vp, i64p, i64p]
+    L.amph_client_finish_verify_dev.argtypes = [vp, vp, i64p, i64p, vp]
+    L.amph_client_finish_mask.argtypes = [vp, vp, sz, vp, vp, i64p, i64p]
+    L.amph_client_finish_mask_dev.argtypes = [vp, vp, sz, vp, vp, i64p, i64p, vp]
+    L.amph_client_finish_mask_json.argtypes = [vp, vp, sz, vp, sz, i64p, i64p]
+    L.amph_client_finish_mask_json_dev.argtypes = [vp, vp, sz, vp, sz, i64p, i64p, vp]
+    L.amph_client_word.argtypes = [vp, sz, vp]
+    L.amph_client_words.restype = sz
+    L.amph_client_words.argtypes = [vp]
+    L.amph_client_parties_seen.argtypes = [vp]
+    L.amph_client_free.restype = None
+    L.amph_client_free.argtypes = [vp]
     return L
 
 
@@ -255,6 +272,12 @@ EXPORTED_PARTY_BATCH = ["amph_parties_begin", "amph_parties_begin_dev", "amph_pa
                         "amph_parties_reset_partner", "amph_parties_finish", "amph_parties_finish_b64",
                         "amph_parties_finish_b64_dev", "amph_parties_free"]
 AMPH_PARTIES_ALL = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+# what include/amphora_client_session.h declares
+EXPORTED_CLIENT_SESSION = ["amph_client_begin", "amph_client_party", "amph_client_finish_verify",
+                           "amph_client_finish_mask", "amph_client_finish_mask_json", "amph_client_word",
+                           "amph_client_words", "amph_client_parties_seen", "amph_client_free",
+                           "amph_client_begin_dev", "amph_client_party_dev", "amph_client_finish_verify_dev",
+                           "amph_client_finish_mask_dev", "amph_client_finish_mask_json_dev"]
 ODO_FIELD_NAMES = ("secretShares", "rShares", "vShares", "wShares", "uShares")
 
 
@@ -1499,6 +1522,26 @@ class Context:
                                                *[_ptr(x) for x in yrv], stream, C.byref(h)))
         return PartySessionsDev(self, h, wo, n_parties, yrv, (share_data, masks32, triples96))
 
+    # -- the client side as a session (include/amphora_client_session.h) -------
+    def client_begin(self, words: int, n_parties: int) -> "ClientSession":
+        """amph_client_begin: a host-mode session that takes each party's five
+        base64 texts as they arrive (ClientSession.party) and finishes from
+        the running sums."""
+        h = C.c_void_p()
+        self._check(lib.amph_client_begin(self._h, words, n_parties, C.byref(h)))
+        return ClientSession(self, h, words, n_parties, None)
+
+    def client_begin_dev(self, words: int, n_parties: int, stream=None) -> "ClientSession":
+        """amph_client_begin_dev: texts, secrets, outputs and verdict words are
+        torch device tensors, every call asynchronous on the ONE stream of the
+        session (`stream`: a torch stream; torch's current stream when None)."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        h = C.c_void_p()
+        self._check(lib.amph_client_begin_dev(self._h, words, n_parties, C.c_void_p(stream.cuda_stream), C.byref(h)))
+        return ClientSession(self, h, words, n_parties, stream)
+
     # -- synthetic device inputs (bench / tests) --------------------------------
     def synth_odos(self, seed: int, n: int, words: int, fault_index: int = -1,
                    noncanon_permille: int = 0, with_plain: bool = False, buf=None):
@@ -1581,6 +1624,143 @@ class PartySession:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             lib.amph_party_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        if lib is not None:
+            self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ClientSession:
+    """One amph_client (include/amphora_client_session.h): each party's five
+    base64 field texts are added into five running sums on the device as they
+    arrive; the finish calls give what recombine_verify_b64 / mask_input_b64 /
+    mask_input_json give on all the texts.  Host mode takes str / bytes /
+    arrays, device mode (Context.client_begin_dev) uint8 device tensors and
+    returns device tensors, asynchronous on the session's stream."""
+
+    def __init__(self, ctx: Context, h, words: int, n_parties: int, stream):
+        self.ctx, self._h, self.words, self.n, self.stream = ctx, h, words, n_parties, stream
+
+    @property
+    def dev(self) -> bool:
+        return self.stream is not None
+
+    def _sp(self):
+        return C.c_void_p(self.stream.cuda_stream)
+
+    def _verdict(self):
+        if self.dev:
+            import torch
+            t = torch.empty(1, dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+            return t, C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_int64))
+        v = C.c_int64(-1)
+        return v, C.pointer(v)
+
+    def _empty(self, shape):
+        if self.dev:
+            import torch
+            return torch.empty(shape, dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+        return np.empty(shape, np.uint8)
+
+    @property
+    def parties_seen(self) -> int:
+        return int(lib.amph_client_parties_seen(self._h))
+
+    def party(self, slot: int, five_texts, bad=None):
+        """Party `slot`'s five field texts (ODO order) into the sums: one
+        launch.  Host: returns -1, raises ValueError with the whole call's
+        message on an illegal base64 character (the slot counts as taken).
+        Device: returns the int64 (1,) verdict tensor (`bad`, or a new one)."""
+        arr, keep = self.ctx._text_structs([five_texts])
+        if self.dev:
+            if not all(_is_dev(k) for k in keep):
+                raise ValueError("a device-mode session takes device tensors")
+            if bad is None:
+                bad, _ = self._verdict()
+            badp = C.cast(C.c_void_p(bad.data_ptr()), C.POINTER(C.c_int64))
+            Context._check(lib.amph_client_party_dev(self._h, slot, arr, badp, self._sp()))
+            return bad
+        if any(_is_dev(k) for k in keep):
+            raise ValueError("a host-mode session takes host buffers")
+        v = C.c_int64(-1)
+        st = lib.amph_client_party(self._h, slot, arr, C.byref(v))
+        if st == AMPH_E_PARAM and v.value >= 0:
+            raise ValueError(lib.amph_last_error().decode())
+        Context._check(st)
+        return v.value
+
+    def _done(self, st, bad):
+        if st == AMPH_E_PARAM and not self.dev and bad.value >= 0:
+            raise ValueError(lib.amph_last_error().decode())
+        if st == AMPH_E_PARAM and self.dev and lib.amph_last_error().startswith(b"Illegal base64 character"):
+            raise ValueError(lib.amph_last_error().decode())
+        Context._check(st, allow_verify=True)
+
+    def finish_verify(self):
+        """-> (canonical secrets (W, 16), first_fail, bad_char), as
+        Context.recombine_verify_b64."""
+        out = self._empty((self.words, 16))
+        ff, ffp = self._verdict()
+        bad, badp = self._verdict()
+        if self.dev:
+            st = lib.amph_client_finish_verify_dev(self._h, _ptr(out), ffp, badp, self._sp())
+        else:
+            st = lib.amph_client_finish_verify(self._h, _ptr(out), ffp, badp)
+        self._done(st, bad)
+        return out, Context._ff_value(ff), Context._ff_value(bad)
+
+    def finish_mask(self, secrets16, records: bool = True, raw: bool = False):
+        """-> (masked (S, 16) or None, records (S, 24) or None, first_fail,
+        bad_char), as Context.mask_input_b64."""
+        sv = words_view(secrets16)
+        if _is_dev(sv) != self.dev:
+            raise ValueError("secrets must live where the session's texts live")
+        S = sv.shape[0]
+        o16 = self._empty((S, 16)) if raw else None
+        o24 = self._empty((S, 24)) if records else None
+        ff, ffp = self._verdict()
+        bad, badp = self._verdict()
+        if self.dev:
+            st = lib.amph_client_finish_mask_dev(self._h, _ptr(sv), S, _ptr(o16), _ptr(o24), ffp, badp, self._sp())
+        else:
+            st = lib.amph_client_finish_mask(self._h, _ptr(sv), S, _ptr(o16), _ptr(o24), ffp, badp)
+        self._done(st, bad)
+        return o16, o24, Context._ff_value(ff), Context._ff_value(bad)
+
+    def finish_mask_json(self, secrets16):
+        """-> (the MaskedInput "data" array text, first_fail, bad_char), as
+        Context.mask_input_json."""
+        sv = words_view(secrets16)
+        if _is_dev(sv) != self.dev:
+            raise ValueError("secrets must live where the session's texts live")
+        S = sv.shape[0]
+        cap = lib.amph_masked_input_data_chars(S)
+        out = self._empty((cap,))
+        ff, ffp = self._verdict()
+        bad, badp = self._verdict()
+        if self.dev:
+            st = lib.amph_client_finish_mask_json_dev(self._h, _ptr(sv), S, _ptr(out), cap, ffp, badp, self._sp())
+        else:
+            st = lib.amph_client_finish_mask_json(self._h, _ptr(sv), S, _ptr(out), cap, ffp, badp)
+        self._done(st, bad)
+        return (out if self.dev else out.tobytes()), Context._ff_value(ff), Context._ff_value(bad)
+
+    def word(self, i: int):
+        """amph_client_word: the recombined (y, r, v, w, u) of word i as ints."""
+        out = np.empty((5, 16), np.uint8)
+        Context._check(lib.amph_client_word(self._h, i, _ptr(out)))
+        return tuple(int.from_bytes(out[k].tobytes(), "little") for k in range(5))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib.amph_client_free(self._h)
         self._h = None
 
     def __del__(self):

@@ -473,6 +473,117 @@ def create_masked_input_bodies(util: SecretShareUtil, secrets: Sequence[Secret],
         lambda o: create_masked_input_body(util, secrets[o], list_of_odo_bodies_lists[o]))
 
 
+class ResponseSession:
+    """The parties' response bodies consumed as they arrive
+    (include/amphora_client_session.h): every body's five base64 member
+    strings go into the running sums on the GPU at once (add_body, one launch
+    per party; any thread may hand in its own party), and secret /
+    masked_input_json / masked_input_body finish from the sums -- the values,
+    bodies and exceptions of verify_vss_json / create_masked_input_json /
+    create_masked_input_body on the same bodies.  The first body fixes the
+    word count; only party 0's body is kept as text (its tags)."""
+
+    def __init__(self, util: SecretShareUtil, n_parties: int):
+        import threading
+        self._util, self._n = util, n_parties
+        self._lock = threading.Lock()
+        self._session = None
+        self._words = None
+        self._body0 = None
+        self._error = None  # the first malformed body / bad character, raised by the finish
+
+    @property
+    def words(self):
+        return self._words
+
+    def add_body(self, party_index: int, body) -> None:
+        from . import wire
+        texts = wire.odo_field_texts(body)[0]
+        if party_index == 0:
+            self._body0 = body
+        with self._lock:
+            try:
+                if self._session is None:
+                    try:
+                        W = wire.words_of_b64(len(texts[0]), texts[0][-2:])
+                    except ValueError as e:
+                        raise AmphoraClientException(str(e)) from e
+                    self._session = self._util.context.client_begin(W, self._n)
+                    self._words = W
+                if any(len(f) != len(texts[0]) for f in texts):
+                    raise AmphoraClientException("The provided shares must be of the same length")
+            except AmphoraClientException as e:
+                self._error = self._error or e
+                raise
+            session = self._session
+        try:
+            _wire_call(session.party, party_index, texts)
+        except AmphoraClientException as e:
+            if isinstance(e.__cause__, _lib.AmphoraNativeError):  # another length than the first body's
+                e = AmphoraClientException("The provided shares must be of the same length")
+                with self._lock:
+                    self._error = self._error or e
+                raise e from None
+            raise  # a bad character: the session keeps the smallest, the finish reports it
+
+    def _finish(self, name: str, *args, **kw):
+        if self._error is not None:
+            raise self._error
+        if self._session is None:
+            raise AmphoraClientException("no response body was added")
+        return _wire_call(getattr(self._session, name), *args, **kw)
+
+    def _raise_for(self, i: int):
+        y, r, v, w, u = self._session.word(i)
+        raise IntegrityVerificationException(self._util.failure_message(y, r, u, v, w))
+
+    def secret(self, secret_id=None):
+        """-> (secretId, tags, canonical secrets), as verify_vss_json."""
+        from . import wire
+        y, ff, _ = self._finish("finish_verify")
+        if ff >= 0:
+            self._raise_for(ff)
+        sid, tags = wire.vss_metadata(self._body0, wire.odo_field_texts(self._body0)[1])
+        return (sid if secret_id is None else secret_id), tags, unpack(y)
+
+    def _mask(self, secret: Secret, fn_name: str, **kw):
+        W = self._words
+        try:
+            res = self._finish(fn_name, pack(secret.data, self._util.prime), **kw)
+        except AmphoraClientException as e:
+            if W is not None and secret.size() > W and isinstance(e.__cause__, _lib.AmphoraNativeError) \
+                    and e.__cause__.status == _lib.AMPH_E_LEN:
+                raise IndexError("Index %d out of bounds for length %d" % (W, W)) from e.__cause__
+            raise
+        if res[-2] >= 0:
+            self._raise_for(res[-2])
+        return res
+
+    def masked_input_json(self, secret: Secret) -> str:
+        """-> the MaskedInput JSON body, as create_masked_input_json."""
+        from . import wire
+        _, rec, _, _ = self._mask(secret, "finish_mask", records=True)
+        return wire.records_to_masked_input_json(secret.secret_id, rec, secret.tags)
+
+    def masked_input_body(self, secret: Secret) -> str:
+        """-> the MaskedInput JSON body, as create_masked_input_body."""
+        import json
+        from . import wire
+        data, _, _ = self._mask(secret, "finish_mask_json")
+        tj = json.dumps([wire._tag_obj(t) for t in secret.tags], separators=(",", ":"))
+        return '{"secretId":"%s","data":%s,"tags":%s}' % (secret.secret_id, data.decode("ascii"), tj)
+
+    def close(self):
+        if self._session is not None:
+            self._session.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def get_secret_data(util: SecretShareUtil, odos: Sequence[OutputDeliveryObject]) -> List[int]:
     """getSecret :206-217 arithmetic (alias of verify_output_delivery_objects)."""
     return verify_output_delivery_objects(util, odos)

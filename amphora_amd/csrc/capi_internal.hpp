@@ -1,12 +1,13 @@
 // Internals shared by the units of the C ABI (capi_*.hip -- capi_ctx,
-// capi_pipeline, capi_words, capi_text, capi_party, parties_session and
-// capi_batch, the many-objects-per-call families): the context, the error and device
+// capi_pipeline, capi_words, capi_text, capi_party, parties_session,
+// client_session and capi_batch, the many-objects-per-call families): the context, the error and device
 // helpers, the word-array pipeline's types and the buffers of one-shot host
 // calls.  Everything here lives in one namespace of hidden
 // visibility: the library exports only what include/amphora.h and its
 // extension headers include/amphora_wire_batch.h,
 // include/amphora_upload_batch.h, include/amphora_respond_batch.h,
-// include/amphora_exchange_batch.h and include/amphora_party_batch.h declare.
+// include/amphora_exchange_batch.h, include/amphora_party_batch.h and
+// include/amphora_client_session.h declare.
 //
 // Host-pointer calls stream the word arrays through the device in batches
 // (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
@@ -38,6 +39,7 @@
 #include "../../include/amphora_respond_batch.h"
 #include "../../include/amphora_exchange_batch.h"
 #include "../../include/amphora_party_batch.h"
+#include "../../include/amphora_client_session.h"
 #include "host_stream.hpp"
 #include "kernels.hpp"
 
@@ -372,5 +374,8 @@ extern const char* const kOdoFieldNames[5];
 const char* b64_field(const amph_odo_b64& o, int k);  // field k's text, in ODO order
 // 1..16 parties and their array: what every wire-text call checks first
 int check_parties(const amph_odo_b64* odos, int n);
+// AMPH_E_PARAM with the wire-text calls' message for a bad_char verdict,
+// (5 party + field) * nchars + offset
+int wire_bad_message(int64_t bad, size_t nchars);
 
 }  // namespace capi

@@ -200,6 +200,12 @@ int check_parties(const amph_odo_b64* odos, int n) {
     return fail(AMPH_E_PARAM, "n_parties must be in [1, 16] with a non-null ODO array");
   return AMPH_OK;
 }
+
+int wire_bad_message(int64_t bad, size_t nchars) {
+  const size_t o = (size_t)bad / nchars, at = (size_t)bad % nchars;
+  return fail(AMPH_E_PARAM, "Illegal base64 character at index " + std::to_string(at) + " of party " +
+                                std::to_string(o / 5) + "'s " + kOdoFieldNames[o % 5]);
+}
 }  // namespace capi
 
 extern "C" {
@@ -324,12 +330,6 @@ int wire_check(const amph_odo_b64* odos, int n, size_t words, size_t* nchars, ui
       if (!b64_field(odos[j], k)) return fail(AMPH_E_PARAM, "null ODO field text");
   }
   return AMPH_OK;
-}
-
-int wire_bad_message(int64_t bad, size_t nchars) {
-  const size_t o = (size_t)bad / nchars, at = (size_t)bad % nchars;
-  return fail(AMPH_E_PARAM, "Illegal base64 character at index " + std::to_string(at) + " of party " +
-                                std::to_string(o / 5) + "'s " + kOdoFieldNames[o % 5]);
 }
 
 // Host mode of the wire-text calls: one launch on the context's first stream

@@ -293,6 +293,25 @@ hipError_t launch_mask_json(const TextSet& tx, int n, size_t words, size_t nchar
                             unsigned long long* first_fail, unsigned long long* bad, const Fp& f,
                             const LaunchCfg& c);
 
+// The client session (include/amphora_client_session.h; wire.hip, "one party
+// at a time"): five running sums of canonical Montgomery words, `words` each.
+struct SumSet {
+  uint4* s[5];  // y, r, v, w, u
+};
+// ONE party's five texts (tx.t[k][0]) decoded in the workgroup and added into
+// the sums (not atomic: launches of one session run in order on one stream);
+// bad_session / bad_call (the latter may be null) min-combine the whole
+// call's (5 party + field) * nchars + offset of an invalid character.
+hipError_t launch_acc_b64(const TextSet& tx, int party, size_t words, size_t nchars, uint32_t pad,
+                          const SumSet& sums, unsigned long long* bad_session, unsigned long long* bad_call,
+                          const Fp& f, const LaunchCfg& c);
+// launch_mask_b64 (out_text null) / launch_mask_json (out_text set, n_secrets
+// >= 1) with the summed fields read from the session's sums; every one of the
+// `words` masks is verified, n_secrets <= words.
+hipError_t launch_mask_sums(const SumSet& sums, size_t words, const uint4* secrets, size_t n_secrets, uint4* out16,
+                            char* out24, char* out_text, unsigned long long* first_fail, const Fp& f,
+                            const LaunchCfg& c);
+
 // K_RV / K_MASK from the wire for many objects in one launch (wire.hip, "the
 // slotted text layout"; wiretiles.hpp): object o's texts start toff[o]
 // characters into every field buffer and its words are packed on

@@ -554,6 +554,79 @@ __global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_json_seg(TextSet tx, 
   mask_tile_out<NP, BS, true>(s.tile, s.words, sec, s.words, acc, nullptr, dst, ff + s.o, lds, f);
 }
 
+// ---- one party at a time: the client session's running sums ---------------------
+// (include/amphora_client_session.h)  The parties' responses reach a client one
+// by one; recombination is a sum mod p of canonical Montgomery words, so a
+// running sum per field is exact in any arrival order.  k_acc_b64 decodes ONE
+// party's five texts exactly as k_rv_b64 does for a single party (the same
+// tile, fast / per-character split and LDS table) and every consumer lane adds
+// its five canonical words into sums[k][word]: a 16-byte load, a mod-p add and
+// a 16-byte store per field -- the decoded words never reach HBM.  The sums
+// are read again by the next party's launch, so the loads and stores are plain
+// (no nontemporal hint).  Launches of one session run in order on one stream:
+// the read-modify-write is not atomic.
+//
+// Bad characters: the decode reports its party-local value (field * nchars +
+// offset) into a workgroup word in LDS; one lane then min-combines the whole
+// call's encoding, (5 party + field) * nchars + offset, into the session's
+// verdict word and into the call's own (bad_call, may be null).
+template <bool BIG, int BS>
+__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_acc_b64(TextSet tx, int party, size_t words, size_t nchars,
+                                            uint32_t pad, SumSet sums, unsigned long long* bad_session,
+                                            unsigned long long* bad_call, Fp f) {
+  __shared__ uint32_t lds[WireGroups<1>::bufs < 2 ? 2 : WireGroups<1>::bufs][3 * BS];
+  __shared__ uint32_t lutw[kLutBytes / 4];
+  __shared__ unsigned long long wg_bad;
+  uint8_t* lutp = reinterpret_cast<uint8_t*>(lutw);
+  b64_lut_fill(lutp);
+  if (threadIdx.x == 0) wg_bad = ~0ULL;
+  __syncthreads();
+  W4 acc[5];
+  uint4 raw[5][1];
+  const bool fast = ((size_t)blockIdx.x + 1) * Wire<BS>::chars + 4 <= nchars;
+  if (fast) {
+    wire_load<1, BS>(tx, raw, blockIdx.x);
+    wire_fields<1, BIG, true, BS>(tx, 1, nchars, pad, words, raw, lds, acc, &wg_bad, f, blockIdx.x, lutp);
+  } else {
+    wire_fields<1, BIG, false, BS>(tx, 1, nchars, pad, words, raw, lds, acc, &wg_bad, f, blockIdx.x, lutp);
+  }
+  const size_t word = (size_t)blockIdx.x * Wire<BS>::words + threadIdx.x;
+  if (threadIdx.x < Wire<BS>::words && word < words) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      uint4* p = sums.s[k] + word;
+      *p = u4(mod_add(w4(*p), acc[k], f));
+    }
+  }
+  __syncthreads();  // every lane's report is in wg_bad
+  if (threadIdx.x == 0 && wg_bad != ~0ULL) {
+    const unsigned long long v = wg_bad + (unsigned long long)(5 * (size_t)party) * nchars;
+    atomicMin(bad_session, v);
+    if (bad_call) atomicMin(bad_call, v);
+  }
+}
+
+// K_MASK from the sums: k_mask_b64 / k_mask_json with acc[5] loaded from the
+// session's sums instead of decoded -- mask_tile_out unchanged, so the tile
+// ownership of the 24-character records and the 37-byte framed records is
+// the whole call's.
+template <int BS, bool JSON>
+__global__ __launch_bounds__(BS) void k_mask_sums(SumSet sums, size_t words, const uint4* secrets, size_t n_secrets,
+                                                  uint4* out16, char* out24, unsigned long long* ff, Fp f) {
+  constexpr int WW = Wire<BS>::words;
+  // (the framed text image of WW records: 37 WW + 4 bytes, as k_mask_json)
+  __shared__ __attribute__((aligned(16))) uint32_t lds[JSON ? 3 : 1][3 * BS];
+  static_assert(3 * 3 * BS * 4 >= kJsonRec * WW + 4, "the text image fits the buffers");
+  W4 acc[5];
+  const size_t word = (size_t)blockIdx.x * WW + threadIdx.x;
+  const bool in = threadIdx.x < WW && word < words;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) acc[k] = w4(in ? sums.s[k][word] : make_uint4(0, 0, 0, 0));
+  uint4 s = make_uint4(0, 0, 0, 0);
+  if (threadIdx.x < WW && word < n_secrets) s = ld(secrets + word);
+  mask_tile_out<1, BS, JSON>(blockIdx.x, words, s, n_secrets, acc, out16, out24, ff, lds, f);
+}
+
 }  // namespace
 
 #ifndef AMPH_WIRE_KERNELS_ONLY  // (tools/ubench: the kernels without the launchers' instantiations)
@@ -633,6 +706,31 @@ hipError_t launch_mask_json_seg(const TextSet& tx, int n, const uint64_t* woff, 
 #define L(NP, BIG) AMPH_LAUNCH((k_mask_json_seg<NP, BIG, BS>), g, dim3(BS), c, tx, n, woff, toff, ooff, n_objects, secrets, out_text, ff, bad, f)
   if (f.big) { AMPH_DISPATCH_NP(n, true, L) } else { AMPH_DISPATCH_NP_SMALL2(n, L) }
 #undef L
+  return hipGetLastError();
+}
+
+hipError_t launch_acc_b64(const TextSet& tx, int party, size_t words, size_t nchars, uint32_t pad,
+                          const SumSet& sums, unsigned long long* bad_session, unsigned long long* bad_call,
+                          const Fp& f, const LaunchCfg& c) {
+  if (words == 0) return hipSuccess;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
+  if (f.big)
+    AMPH_LAUNCH((k_acc_b64<true, BS>), g, dim3(BS), c, tx, party, words, nchars, pad, sums, bad_session, bad_call, f);
+  else
+    AMPH_LAUNCH((k_acc_b64<false, BS>), g, dim3(BS), c, tx, party, words, nchars, pad, sums, bad_session, bad_call, f);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_sums(const SumSet& sums, size_t words, const uint4* secrets, size_t n_secrets, uint4* out16,
+                            char* out24, char* out_text, unsigned long long* ff, const Fp& f, const LaunchCfg& c) {
+  if (words == 0) return hipSuccess;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
+  if (out_text)
+    AMPH_LAUNCH((k_mask_sums<BS, true>), g, dim3(BS), c, sums, words, secrets, n_secrets, nullptr, out_text, ff, f);
+  else
+    AMPH_LAUNCH((k_mask_sums<BS, false>), g, dim3(BS), c, sums, words, secrets, n_secrets, out16, out24, ff, f);
   return hipGetLastError();
 }
 

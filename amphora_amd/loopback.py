@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Dict, List, Sequence
 
 from . import _lib
-from .client import (SecretShareUtil, create_masked_input, create_masked_input_body,
+from .client import (ResponseSession, SecretShareUtil, create_masked_input, create_masked_input_body,
                      create_masked_input_json, verify_output_delivery_objects, verify_vss_json)
 from .entities import (AmphoraClientException, AmphoraServiceException, FactorPair,
                        IllegalArgumentException, MaskedInput, MultiplicationExchangeObject,
@@ -151,9 +151,13 @@ class LoopbackAmphoraClient:
         transport="wire": as "json", but the upload hop stays text at both
         ends: the client's kernel writes the framed "data" array
         (client.create_masked_input_body) and every party converts the body's
-        text (AmphoraParty.upload_masked_input_body)."""
-        if transport not in ("objects", "json", "wire"):
-            raise ValueError("transport must be 'objects', 'json' or 'wire'")
+        text (AmphoraParty.upload_masked_input_body).
+        transport="session": as "wire", but each worker of the fan-out hands
+        its party's body to a client.ResponseSession the moment the party
+        returns, so all but the last response are decoded and summed on the
+        GPU while the client still waits for the slowest party."""
+        if transport not in ("objects", "json", "wire", "session"):
+            raise ValueError("transport must be 'objects', 'json', 'wire' or 'session'")
         self.parties = list(parties)
         self.util = SecretShareUtil.of(prime, r, r_inv, device)
         self.transport = transport
@@ -192,7 +196,36 @@ class LoopbackAmphoraClient:
                 msg += "\n\t" + REQUEST_FOR_ENDPOINT_FAILED_EXCEPTION_MSG % (self.uri(p), e)
             raise AmphoraClientException(msg)
 
+    def _fan_in(self, fetch) -> ResponseSession:
+        """Fan out fetch(party) -> body and add every body to a
+        ResponseSession as it arrives.  A body the session refuses (malformed,
+        or an illegal base64 character) fails no request: the session's finish
+        raises it, as the whole call on all the bodies does."""
+        rs = ResponseSession(self.util, len(self.parties))
+        index = {id(p): i for i, p in enumerate(self.parties)}
+
+        def worker(p):
+            body = fetch(p)
+            try:
+                rs.add_body(index[id(p)], body)
+            except AmphoraClientException:
+                pass
+
+        try:
+            self._unwrap(self._fan_out(worker))
+        except Exception:
+            rs.close()
+            raise
+        return rs
+
     def create_secret(self, secret: Secret) -> uuid.UUID:
+        if self.transport == "session":
+            from . import wire
+            with self._fan_in(lambda p: wire.odo_to_json(
+                    p.ctx, p.get_input_masks(secret.secret_id, secret.size()))) as rs:
+                text = rs.masked_input_body(secret)
+            self._check_success(self._fan_out(lambda p: p.upload_masked_input_body(text)))
+            return secret.secret_id
         if self.transport == "wire":
             from . import wire
             bodies = self._unwrap(self._fan_out(lambda p: wire.odo_to_json(
@@ -215,6 +248,13 @@ class LoopbackAmphoraClient:
 
     def get_secret(self, secret_id: uuid.UUID) -> Secret:
         request_id = uuid.uuid4()
+        if self.transport == "session":
+            from . import wire
+            with self._fan_in(lambda p: wire.vss_to_json(
+                    p.ctx, secret_id, p.secrets[secret_id].tags, p.get_secret_share(secret_id, request_id),
+                    pretty=False)) as rs:
+                sid, tags, data = rs.secret(secret_id)
+            return Secret(sid, tags, data)
         if self.transport in ("json", "wire"):
             from . import wire
             bodies = self._unwrap(self._fan_out(lambda p: wire.vss_to_json(

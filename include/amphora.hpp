@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "amphora.h"
+#include "amphora_client_session.h"
 
 namespace amphora {
 
@@ -536,6 +537,105 @@ inline std::string maskSecretDataText(const SecretShareUtil& util, const std::ve
   check(st);
   return text;
 }
+
+// The parties' response texts consumed as they arrive
+// (include/amphora_client_session.h): addTexts hands one party's five base64
+// field strings to the GPU at once -- one launch adds them into the running
+// sums, any thread may hand in its own party -- and secrets / maskSecretText /
+// maskSecretDataText finish from the sums: the values and exceptions of
+// verifyOutputDeliveryText / maskSecretText / maskSecretDataText on the same
+// texts.  The first texts fix the word count.  A session finishes once.
+class ResponseSession {
+ public:
+  ResponseSession(const SecretShareUtil& util, int nParties) : util_(util), n_(nParties) {}
+  ResponseSession(const ResponseSession&) = delete;
+  ResponseSession& operator=(const ResponseSession&) = delete;
+  ~ResponseSession() { amph_client_free(h_); }
+
+  // A bad character is thrown here as AmphoraClientException and again by the
+  // finish call (with the smallest over all parties, the whole call's text);
+  // texts of another length than the first party's: IllegalArgumentException.
+  void addTexts(int party, const std::string& secretShares, const std::string& rShares,
+                const std::string& vShares, const std::string& wShares, const std::string& uShares) {
+    const std::string* f[5] = {&secretShares, &rShares, &vShares, &wShares, &uShares};
+    for (int k = 1; k < 5; ++k)
+      if (f[k]->size() != f[0]->size())
+        throw IllegalArgumentException("The provided shares must be of the same length");
+    if (!h_) {
+      words_ = wordsOfBase64(secretShares);
+      check(amph_client_begin(util_.context().get(), words_, n_, &h_));
+    }
+    const amph_odo_b64 t{f[0]->data(), f[1]->data(), f[2]->data(), f[3]->data(), f[4]->data(), f[0]->size()};
+    int64_t bad = -1;
+    const int st = amph_client_party(h_, party, &t, &bad);
+    if (st == AMPH_E_PARAM && bad >= 0) throw AmphoraClientException(amph_last_error());
+    if (st == AMPH_E_LEN) throw IllegalArgumentException("The provided shares must be of the same length");
+    check(st);
+  }
+  void addTexts(int party, const OdoText& t) { addTexts(party, t.f[0], t.f[1], t.f[2], t.f[3], t.f[4]); }
+
+  size_t words() const { return words_; }
+
+  // verifyOutputDeliveryText from the sums
+  std::vector<u128> secrets() {
+    Bytes out(words_ * 16);
+    int64_t ff = -1, bad = -1;
+    const int st = amph_client_finish_verify(handle(), out.data(), &ff, &bad);
+    done(st, ff, bad, 0);
+    return unpackWords(out);
+  }
+
+  // maskSecretText from the sums
+  std::vector<std::string> maskSecretText(const std::vector<u128>& secret) {
+    const Bytes in = reduced(secret);
+    std::string rec(24 * secret.size(), '\0');
+    int64_t ff = -1, bad = -1;
+    const int st = amph_client_finish_mask(handle(), in.data(), secret.size(), nullptr, &rec[0], &ff, &bad);
+    done(st, ff, bad, secret.size());
+    std::vector<std::string> out;
+    for (size_t i = 0; i < secret.size(); ++i) out.push_back(rec.substr(24 * i, 24));
+    return out;
+  }
+
+  // maskSecretDataText from the sums
+  std::string maskSecretDataText(const std::vector<u128>& secret) {
+    const Bytes in = reduced(secret);
+    std::string text(amph_masked_input_data_chars(secret.size()), '\0');
+    int64_t ff = -1, bad = -1;
+    const int st =
+        amph_client_finish_mask_json(handle(), in.data(), secret.size(), &text[0], text.size(), &ff, &bad);
+    done(st, ff, bad, secret.size());
+    return text;
+  }
+
+ private:
+  amph_client* handle() {
+    if (!h_) check(amph_client_begin(util_.context().get(), 0, n_, &h_));  // no texts: every slot is missing
+    return h_;
+  }
+  Bytes reduced(const std::vector<u128>& secret) const {
+    std::vector<u128> s(secret);
+    for (auto& x : s) x %= util_.getPrime();
+    return packWords(s);
+  }
+  void done(int st, int64_t ff, int64_t bad, size_t nSecrets) {
+    if (st == AMPH_E_PARAM && bad >= 0) throw AmphoraClientException(amph_last_error());
+    if (st == AMPH_E_VERIFY) {  // the reference message, from the five sums of word ff
+      uint8_t w[5][16];
+      check(amph_client_word(h_, (size_t)ff, w));
+      throw IntegrityVerificationException(
+          util_.message(loadLe(w[0]), loadLe(w[1]), loadLe(w[4]), loadLe(w[2]), loadLe(w[3])));
+    }
+    if (st == AMPH_E_LEN && nSecrets > words_)
+      throw std::out_of_range("Index " + std::to_string(words_) + " out of bounds for length " +
+                              std::to_string(words_));
+    check(st);
+  }
+  const SecretShareUtil& util_;
+  int n_;
+  size_t words_ = 0;
+  amph_client* h_ = nullptr;
+};
 
 }  // namespace client
 

@@ -65,6 +65,29 @@ final class NativeShareArithmetic {
       long ctx, byte[][] y, byte[][] r, byte[][] v, byte[][] w, byte[][] u, long words,
       byte[] secretsLe, byte[] outRecords24);
 
+  /**
+   * amph_client_begin: a session that takes each party's five base64 strings as they arrive
+   * (ResponseSession); every party's fields hold `words` 16-byte words
+   */
+  static native long clientBegin(long ctx, long words, int nParties);
+
+  /** one party's five base64 strings (ASCII), parties in any order, each once: one launch */
+  static native void clientParty(long session, int party, byte[] y, byte[] r, byte[] v, byte[] w, byte[] u);
+
+  /** getSecret from the running sums: -1 or the failing word */
+  static native long clientFinishVerify(long session, byte[] outLe);
+
+  /** createSecret from the running sums: the 24-character MaskedInputData records */
+  static native long clientFinishMask(long session, byte[] secretsLe, byte[] outRecords24);
+
+  /** the same with the records framed as the MaskedInput "data" array text (37 S + 1 characters) */
+  static native long clientFinishMaskJson(long session, byte[] secretsLe, byte[] outText);
+
+  /** the recombined y, r, v, w, u of one word: 5 x 16 canonical LE bytes */
+  static native byte[] clientWord(long session, long index);
+
+  static native void clientFree(long session);
+
   /** LE16 of x mod p (x reduced only when negative or wider than 128 bits, as the kernels
    * canonicalise any 128-bit word themselves) */
   static void putWord(BigInteger x, BigInteger prime, byte[] out, int word) {

@@ -192,6 +192,11 @@ class SecretShareUtil implements AutoCloseable {
     return masked;
   }
 
+  /** the native context, for the classes of this package that run on it (ResponseSession) */
+  long nativeContext() {
+    return ctx;
+  }
+
   private boolean inField(BigInteger x) {
     return x.signum() >= 0 && x.compareTo(prime) < 0;
   }

@@ -496,6 +496,121 @@ JNIEXPORT jlong JNICALL CLIENT(maskInputB64)(JNIEnv* env, jclass cls, jlong ctx,
   return st == AMPH_E_VERIFY ? (jlong)fail : -1;
 }
 
+/* ---- the client side as a session (ResponseSession.java) -------------------------
+   Arrays above AMPH_JNI_REGION_BYTES are staged in native copies (region
+   copies), smaller ones pinned: a party call waits for the GPU. */
+static int client_arrays_in(JNIEnv* env, Pin* pins, int count, int first_output, int* staged) {
+  *staged = total_len(pins, count) > region_bytes();
+  return *staged ? stage_native(env, pins, count, first_output) : pin_all(env, pins, count);
+}
+
+static void client_arrays_out(JNIEnv* env, Pin* pins, int count, int first_output, int staged, int commit) {
+  if (staged) unstage_native(env, pins, count, first_output, commit);
+  else unpin_all(env, pins, count, first_output);
+}
+
+JNIEXPORT jlong JNICALL CLIENT(clientBegin)(JNIEnv* env, jclass cls, jlong ctx, jlong words, jint nParties) {
+  (void)cls;
+  if (words < 0) return throw_arg(env, "negative word count"), 0;
+  void* session = NULL;
+  const int st = amphj_client_begin(CTX(ctx), (size_t)words, nParties, &session);
+  if (st != AMPH_OK) {
+    throw_status(env, st);
+    return 0;
+  }
+  return (jlong)(intptr_t)session;
+}
+
+/* one party's five base64 strings (ASCII bytes), in any order of the parties */
+JNIEXPORT void JNICALL CLIENT(clientParty)(JNIEnv* env, jclass cls, jlong session, jint party, jbyteArray y,
+                                           jbyteArray r, jbyteArray v, jbyteArray w, jbyteArray u) {
+  (void)cls;
+  if (!session) return (void)throw_arg(env, "null client session");
+  jbyteArray a[5] = {y, r, v, w, u};
+  Pin pins[5];
+  for (int k = 0; k < 5; ++k)
+    if (ref(env, a[k], &pins[k])) return;
+  int staged;
+  if (client_arrays_in(env, pins, 5, 5, &staged)) return;
+  const uint8_t* ptrs[5];
+  size_t lens[5];
+  ptrs_of(pins, 5, ptrs, lens);
+  const int st = amphj_client_party(CTX(session), party, (const char* const*)ptrs, lens);
+  client_arrays_out(env, pins, 5, 5, staged, 0);
+  if (st != AMPH_OK) throw_status(env, st);
+}
+
+/* getSecret from the sums -> -1 or the failing word */
+JNIEXPORT jlong JNICALL CLIENT(clientFinishVerify)(JNIEnv* env, jclass cls, jlong session, jbyteArray out) {
+  (void)cls;
+  if (!session) return throw_arg(env, "null client session");
+  Pin pin;
+  if (ref(env, out, &pin)) return -1;
+  int staged;
+  if (client_arrays_in(env, &pin, 1, 0, &staged)) return -1;
+  int64_t fail = -1;
+  const int st = amphj_client_finish_verify(CTX(session), (uint8_t*)pin.p, (size_t)pin.len, &fail);
+  client_arrays_out(env, &pin, 1, 0, staged, st == AMPH_OK);
+  if (st != AMPH_OK && st != AMPH_E_VERIFY) throw_status(env, st);
+  return st == AMPH_E_VERIFY ? (jlong)fail : -1;
+}
+
+/* createSecret from the sums: verify + mask + the 24-character MaskedInputData records */
+JNIEXPORT jlong JNICALL CLIENT(clientFinishMask)(JNIEnv* env, jclass cls, jlong session, jbyteArray secrets,
+                                                 jbyteArray records) {
+  (void)cls;
+  if (!session) return throw_arg(env, "null client session");
+  Pin pins[2];
+  if (ref(env, secrets, &pins[0]) || ref(env, records, &pins[1])) return -1;
+  int staged;
+  if (client_arrays_in(env, pins, 2, 1, &staged)) return -1;
+  int64_t fail = -1;
+  const int st = amphj_client_finish_mask(CTX(session), (const uint8_t*)pins[0].p, (size_t)pins[0].len,
+                                          (char*)pins[1].p, (size_t)pins[1].len, &fail);
+  client_arrays_out(env, pins, 2, 1, staged, st == AMPH_OK);
+  if (st != AMPH_OK && st != AMPH_E_VERIFY) throw_status(env, st);
+  return st == AMPH_E_VERIFY ? (jlong)fail : -1;
+}
+
+/* the same with the records framed as the MaskedInput "data" array text */
+JNIEXPORT jlong JNICALL CLIENT(clientFinishMaskJson)(JNIEnv* env, jclass cls, jlong session, jbyteArray secrets,
+                                                     jbyteArray text) {
+  (void)cls;
+  if (!session) return throw_arg(env, "null client session");
+  Pin pins[2];
+  if (ref(env, secrets, &pins[0]) || ref(env, text, &pins[1])) return -1;
+  int staged;
+  if (client_arrays_in(env, pins, 2, 1, &staged)) return -1;
+  int64_t fail = -1;
+  const int st = amphj_client_finish_mask_json(CTX(session), (const uint8_t*)pins[0].p, (size_t)pins[0].len,
+                                               (char*)pins[1].p, (size_t)pins[1].len, &fail);
+  client_arrays_out(env, pins, 2, 1, staged, st == AMPH_OK);
+  if (st != AMPH_OK && st != AMPH_E_VERIFY) throw_status(env, st);
+  return st == AMPH_E_VERIFY ? (jlong)fail : -1;
+}
+
+/* the recombined y, r, v, w, u of one word: 5 x 16 canonical LE bytes */
+JNIEXPORT jbyteArray JNICALL CLIENT(clientWord)(JNIEnv* env, jclass cls, jlong session, jlong index) {
+  (void)cls;
+  if (!session) return throw_arg(env, "null client session"), NULL;
+  if (index < 0) return throw_arg(env, "negative word index"), NULL;
+  jbyte b[80];
+  const int st = amphj_client_word(CTX(session), (size_t)index, (uint8_t*)b, sizeof b);
+  if (st != AMPH_OK) {
+    throw_status(env, st);
+    return NULL;
+  }
+  jbyteArray out = (*env)->NewByteArray(env, 80);
+  if (out) (*env)->SetByteArrayRegion(env, out, 0, 80, b);
+  return out;
+}
+
+JNIEXPORT void JNICALL CLIENT(clientFree)(JNIEnv* env, jclass cls, jlong session) {
+  (void)env;
+  (void)cls;
+  amphj_client_free(CTX(session));
+}
+
 /* ---- service ------------------------------------------------------------------ */
 #define SERVICE(name) Java_io_carbynestack_amphora_service_calculation_NativeShareArithmetic_##name
 

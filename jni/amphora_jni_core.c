@@ -194,6 +194,61 @@ int amphj_mask_input_b64(void* ctx, int n, const char* const* texts, const size_
                                  NULL));
 }
 
+int amphj_client_begin(void* ctx, size_t words, int n_parties, void** session) {
+  amph_client* s = NULL;
+  const int st = abi(amph_client_begin((amph_ctx*)ctx, words, n_parties, &s));
+  *session = s;
+  return st;
+}
+
+int amphj_client_party(void* session, int party, const char* const* texts, const size_t* lens) {
+  if (!session) return set_msg(AMPH_E_PARAM, "null client session");
+  for (int k = 1; k < 5; ++k)
+    if (lens[k] != lens[0]) return set_msg(AMPH_E_LEN, kSameLength);
+  const amph_odo_b64 t = {texts[0], texts[1], texts[2], texts[3], texts[4], lens[0]};
+  int64_t bad = -1;
+  return abi(amph_client_party((amph_client*)session, party, &t, &bad));
+}
+
+int amphj_client_finish_verify(void* session, uint8_t* out, size_t out_len, int64_t* fail) {
+  *fail = -1;
+  if (!session) return set_msg(AMPH_E_PARAM, "null client session");
+  if (room(out_len, 16 * amph_client_words((const amph_client*)session), "the secrets array")) return AMPH_E_LEN;
+  int64_t bad = -1;
+  return abi(amph_client_finish_verify((amph_client*)session, out, fail, &bad));
+}
+
+int amphj_client_finish_mask(void* session, const uint8_t* secrets, size_t secrets_len, char* records24,
+                             size_t records_len, int64_t* fail) {
+  *fail = -1;
+  if (!session) return set_msg(AMPH_E_PARAM, "null client session");
+  const size_t S = secrets_len / 16;
+  if (room(records_len, 24 * S, "the record array")) return AMPH_E_LEN;
+  int64_t bad = -1;
+  return abi(amph_client_finish_mask((amph_client*)session, secrets, S, NULL, records24, fail, &bad));
+}
+
+int amphj_client_finish_mask_json(void* session, const uint8_t* secrets, size_t secrets_len, char* text,
+                                  size_t text_len, int64_t* fail) {
+  *fail = -1;
+  if (!session) return set_msg(AMPH_E_PARAM, "null client session");
+  const size_t S = secrets_len / 16;
+  /* more secrets than masks: the ABI verifies first and writes nothing */
+  if (S <= amph_client_words((const amph_client*)session) &&
+      room(text_len, amph_masked_input_data_chars(S), "the data array text"))
+    return AMPH_E_LEN;
+  int64_t bad = -1;
+  return abi(amph_client_finish_mask_json((amph_client*)session, secrets, S, text, text_len, fail, &bad));
+}
+
+int amphj_client_word(void* session, size_t index, uint8_t* out, size_t out_len) {
+  if (!session) return set_msg(AMPH_E_PARAM, "null client session");
+  if (room(out_len, 5 * 16, "the word array")) return AMPH_E_LEN;
+  return abi(amph_client_word((amph_client*)session, index, (uint8_t(*)[16])out));
+}
+
+void amphj_client_free(void* session) { amph_client_free((amph_client*)session); }
+
 int amphj_convert_share(void* ctx, const uint8_t* masked, size_t masked_len, const uint8_t* tuples,
                         size_t tuples_len, const uint8_t* mac_key_le, size_t key_len, int use_zero_input_as_data,
                         uint8_t* out, size_t out_len) {

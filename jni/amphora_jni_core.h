@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "amphora.h"
+#include "amphora_client_session.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -67,6 +68,23 @@ int amphj_recombine_verify_b64(void* ctx, int n, const char* const* texts, const
 int amphj_mask_input_b64(void* ctx, int n, const char* const* texts, const size_t* lens, size_t words,
                          const uint8_t* secrets, size_t secrets_len, char* records24,
                          size_t records_len, int64_t* fail);
+
+/* the client side as a session (amph_client_*, include/amphora_client_session.h):
+ * each party's five base64 texts (ASCII; texts[k] / lens[k] in ODO order) as
+ * they arrive, the finish from the running sums.  A bad character:
+ * AMPH_E_PARAM with the whole call's message, from the party call and again
+ * from the finish. */
+int amphj_client_begin(void* ctx, size_t words, int n_parties, void** session);
+int amphj_client_party(void* session, int party, const char* const* texts, const size_t* lens);
+int amphj_client_finish_verify(void* session, uint8_t* out, size_t out_len, int64_t* fail);
+int amphj_client_finish_mask(void* session, const uint8_t* secrets, size_t secrets_len, char* records24,
+                             size_t records_len, int64_t* fail);
+/* text_len at least amph_masked_input_data_chars(secrets_len / 16) */
+int amphj_client_finish_mask_json(void* session, const uint8_t* secrets, size_t secrets_len, char* text,
+                                  size_t text_len, int64_t* fail);
+/* out: 5 x 16 bytes, the recombined y, r, v, w, u of word `index` (canonical LE16) */
+int amphj_client_word(void* session, size_t index, uint8_t* out, size_t out_len);
+void amphj_client_free(void* session);
 
 /* ---- service ------------------------------------------------------------ */
 int amphj_convert_share(void* ctx, const uint8_t* masked, size_t masked_len, const uint8_t* tuples,
