@@ -1,6 +1,6 @@
 """Edge primes, carry-chain operands and plain Python-int references shared by
-tests/test_field_host.py, tests/test_oracle_primes.py and
-tests/test_hip_primes.py.
+tests/test_field_host.py, tests/test_oracle_primes.py,
+tests/test_session_cases_cpu.py and tests/test_hip_primes.py.
 
 Every reference here is written with ``%`` and ``pow`` on Python ints (no
 Montgomery tricks); every coverage predicate is computed on the inputs alone,
@@ -285,7 +285,9 @@ def odo_rows(pid: str, n: int) -> Rows:
     (y, r) stay E x E mod p at every n (the products 0 and p - 1 stay
     reachable); w = y r and u = v r are computed with Python ints, the last
     party's w / u share closing the sum.  Closing shares are written canonical
-    on even words and + k p on odd ones."""
+    on even words and + k p on odd ones; at words 1 and 3 party 0's w / u
+    share is chosen so that the closing share is 1 (1 + k p fits below 2^128
+    on every prime: the closing party holds words >= p in all five fields)."""
     pr = BY_ID[pid]
     E = edge_words(pr.p)
     L = len(E)
@@ -315,6 +317,10 @@ def odo_rows(pid: str, n: int) -> Rows:
                 sh = E[(i + 11 * j + k) % L]
                 parties[j][k][i] = sh
                 rest = (rest - sh) % pr.p
+            if n >= 2 and i in (1, 3):  # the closing share is 1 here, so that + k p fits on every prime:
+                # above 2^128 - 2^8 (max128) the walk alone leaves the closing party's w / u canonical
+                parties[0][k][i] = (parties[0][k][i] + rest - 1) % pr.p
+                rest = 1
             parties[n - 1][k][i] = lift(pr, rest, i)
     return Rows(W, n, tuple(tuple(tuple(f) for f in o) for o in parties), tuple(ys), tuple(rs), tuple(vs),
                 tuple(ws), tuple(us))
@@ -362,6 +368,115 @@ def rv_coverage(pr: Prime, rows: Rows):
                     carries += acc + x >= M128
                     acc = (acc + x) % pr.p
         assert carries, pr.id
+
+
+# ---- a running sum: the client session takes the parties one at a time -------------
+def session_orders(n: int) -> list:
+    """The arrival orders the session tests use: forward, reverse and one
+    fixed permutation (odd slots first, then the even ones); equal orders
+    (n <= 2) once."""
+    fwd = list(range(n))
+    out = []
+    for order in (fwd, fwd[::-1], fwd[1::2] + fwd[0::2]):
+        if order not in out:
+            out.append(order)
+    return out
+
+
+def session_coverage(pr: Prime, rows: Rows, order) -> dict:
+    """What a running sum per field meets when the parties of `rows` arrive in
+    `order`: acc starts at 0 and every step adds the party's canonical word,
+    acc = (acc + x mod p) mod p.  Counted over all five fields:
+
+    * carry      steps with acc + x >= 2^128 (the add needs its 129th bit);
+    * exact_p    steps with acc + x == p (the final subtract's equality);
+    * p_minus_1  steps with acc + x == p - 1 (the largest sum left alone);
+    * noncanon   per party (by slot) its five per-field counts of words >= p;
+
+    with a witness each for the tests that read single words back: carry_at /
+    exact_p_at, the smallest word index with such a step, an inner word
+    (neither 0 nor W - 1) where there is one (None if no step qualifies).
+    Python ints on the inputs alone."""
+    p = pr.p
+    cov = {"carry": 0, "exact_p": 0, "p_minus_1": 0,
+           "noncanon": [tuple(sum(1 for w in f if w >= p) for f in o) for o in rows.odos]}
+    at = {"carry": set(), "exact_p": set()}
+    for k in range(5):
+        fields = [rows.odos[j][k] for j in order]
+        for i in range(rows.W):
+            acc = 0
+            for f in fields:
+                s = acc + f[i] % p
+                if s >= M128:
+                    cov["carry"] += 1
+                    at["carry"].add(i)
+                if s == p:
+                    cov["exact_p"] += 1
+                    at["exact_p"].add(i)
+                elif s == p - 1:
+                    cov["p_minus_1"] += 1
+                acc = s - p if s >= p else s
+    for name, seen in at.items():
+        inner = [i for i in seen if 0 < i < rows.W - 1]
+        cov[name + "_at"] = min(inner or seen, default=None)
+    return cov
+
+
+def assert_session_coverage(pr: Prime, rows: Rows, order) -> dict:
+    """Sums of exactly p and p - 1 at n >= 2 on every prime; a carry out of bit
+    127 at n >= 2 on a BIG prime and never otherwise (2 p <= 2^128 below
+    2^127, and the first party is added to 0); words >= p in every field of
+    the party that arrives first and of the one that arrives last."""
+    assert sorted(order) == list(range(rows.n)), order
+    cov = session_coverage(pr, rows, order)
+    if rows.n >= 2:
+        assert cov["exact_p"] and cov["p_minus_1"], (pr.id, rows.n, order, cov)
+    if pr.big and rows.n >= 2:
+        assert cov["carry"] and cov["carry_at"] is not None, (pr.id, rows.n, order, cov)
+    else:
+        assert cov["carry"] == 0, (pr.id, rows.n, order, cov)
+    for j in (order[0], order[-1]):
+        assert all(cov["noncanon"][j]), (pr.id, rows.n, j, cov["noncanon"][j])
+    return cov
+
+
+def running_sums(pr: Prime, rows: Rows, order) -> list:
+    """The five canonical Montgomery sums after every party of `order` is in:
+    [k][i], the word the session holds for field k of word i
+    (amph_client_word returns from_gfp of it)."""
+    return [[sum(rows.odos[j][k][i] % pr.p for j in order) % pr.p for i in range(rows.W)] for k in range(5)]
+
+
+# ---- which test launches both forms of a `template <..., bool BIG, ...>` kernel --------
+# {kernel: the test of tests/test_hip_primes.py that runs it on all eight primes (three BIG, five not)};
+# tests/test_session_cases_cpu.py holds this table against amphora_amd/csrc/*.hip.
+BIG_KERNELS = {
+    "k_rv": "test_recombine_verify",
+    "k_mask": "test_mask_input",
+    "k_rv_seg": "test_packed",
+    "k_mask_seg": "test_packed",
+    "k_recombine": "test_recombine_then_verify_columns",
+    "k_verify": "test_recombine_then_verify_columns",
+    "k_conv": "test_convert_share",
+    "k_conv_json": "test_convert_share",
+    "k_conv_json_seg": "test_convert_share_json_packed",
+    "k_open": "test_open_and_post",
+    "k_odo_post": "test_open_and_post",
+    "k_open_post": "test_open_and_post",
+    "k_open_post_seg": "test_party_sessions",
+    "k_to_gfp": "test_codecs",
+    "k_mask_words": "test_codecs",
+    "k_synth": "test_device_synth",
+    "k_synth_words": "test_device_synth",
+    "k_rv_b64": "test_wire_fused",
+    "k_mask_b64": "test_wire_fused",
+    "k_mask_json": "test_wire_fused",
+    "k_rv_b64_seg": "test_wire_packed",
+    "k_mask_b64_seg": "test_wire_packed",
+    "k_mask_json_seg": "test_wire_packed",
+    "k_acc_b64": "test_client_session",
+}
+BIG_KERNELS_LEFT_OUT = {}  # {kernel: why no test of test_hip_primes.py launches both of its forms}
 
 
 PostRows = namedtuple("PostRows", "W triples own partners")

@@ -8,7 +8,11 @@ itself is pinned on the CPU by tests/test_oracle_primes.py).
 This launches the BIG and the !BIG instantiation of every arithmetic kernel
 (K_RV, K_MASK, recombine, verify, the codecs, K_CONV, K_ODO_PRE, open,
 K_ODO_POST, the fused open + post, the wire-fused and segmented kernels, the
-party session, the synthetic inputs), pins the device lowering of
+party session, the synthetic inputs; the batch and session kernels:
+k_rv_b64_seg / k_mask_b64_seg / k_mask_json_seg, k_conv_json_seg,
+k_open_post_seg behind the parties session's exchange decode, and the client
+session's k_acc_b64 with k_mask_sums and K_RV over its running sums --
+tests/field_cases.py BIG_KERNELS names the test for each), pins the device lowering of
 addc / subc / macc96 (mont_mul_ps runs in the wire kernels and for K_MASK's
 secret product, mont_mul_cios in K_RV: both are compared with the same
 reference), and sends partner diffs with raw magnitudes (>= p, negative zero,
@@ -422,6 +426,269 @@ def test_party_session(env, n):
             w, u = s.finish(j == 0)
             assert np.array_equal(w, ow) and np.array_equal(u, ou)
         s.close()
+
+
+# ---- many requests in one parties session (k_open_post_seg behind the exchange decode) ------------------
+@pytest.mark.parametrize("n", [2, 3])
+def test_party_sessions(env, n):
+    """test_party_session's inputs cut into requests of 1, 63, 1, 64 and the
+    rest of the words: 126, 128 and more than 128 pairs against the 128-pair
+    tile.  Every party on the host calls; at n = 2 on the device calls too."""
+    import torch
+    pr = env.pr
+    L = len(FC.edge_words(pr.p))
+    W = L * L // 2
+    woff = np.array([0, 1, 64, 65, 129, W], np.uint64)
+    cuts = [(int(a), int(b)) for a, b in zip(woff, woff[1:])]
+    assert [b - a for a, b in cuts[:4]] == [1, 63, 1, 64] and W - 129 > 64
+    ins = [party_inputs(pr, j, W) for j in range(n)]
+    own = [FC.odo_pre(pr, *ins[j]) for j in range(n)]
+    mags = [x for o in own for pair in o for x in map(abs, pair)]
+    assert max(mags) == pr.p - 1  # the longest decimal magnitude the text can carry ...
+    assert all(max(map(abs, o[0])) == pr.p - 1 for o in own)  # ... in the first request, of every party
+    if pr.id == "max128":
+        assert len(str(max(mags))) == 39
+    arrays = []
+    for j in range(n):
+        ys, m1s, m2s, triples = ins[j]
+        share = FC.arr([x for y in ys for x in (y, FC.MASK128 - y)], 32)
+        masks = FC.arr([x for i in range(W) for x in (m1s[i], 1, m2s[i], 2)], 32)
+        trip = FC.arr([x for a, b, c in triples for x in (a, 3, b, 4, c, 5)], 96)
+        arrays.append((share, masks, trip))
+    pre = [env.F.odo_pre(a[0], 32, a[1], a[2]) for a in arrays]
+    want_texts, want_wu, want_fields = [], [], []
+    for j in range(n):
+        assert FC.signed_of(pre[j][3], pre[j][4]) == own[j]
+        want_texts.append([jackson_text(own[j][2 * a:2 * b]) for a, b in cuts])
+        others = [k for k in range(n) if k != j]
+        flat = [[x for pair in own[k] for x in pair] for k in [j] + others]
+        o = FC.open_values(pr, flat)
+        z = [FC.post_word(pr, D, E, t, j == 0) for (D, E), t in zip(zip(o[0::2], o[1::2]), ins[j][3])]
+        ow, ou = env.F.odo_post(env.F.recombine_diffs([pre[k][3] for k in [j] + others],
+                                                      [pre[k][4] for k in [j] + others]), arrays[j][2], j == 0)
+        assert FC.ints(ow) == z[0::2] and FC.ints(ou) == z[1::2]
+        want_wu.append((ow, ou))
+        five = [FC.arr(ins[j][0]), FC.arr(ins[j][1]), FC.arr(ins[j][2]), ow, ou]
+        want_fields.append([[base64.b64encode(x[a:b].tobytes()) for x in five] for a, b in cuts])
+    sessions = [env.ctx.parties_begin(arrays[j][0], 32, arrays[j][1], arrays[j][2], woff, n) for j in range(n)]
+    for j, s in enumerate(sessions):
+        assert FC.ints(s.y) == ins[j][0] and FC.ints(s.r) == ins[j][1] and FC.ints(s.v) == ins[j][2]
+        assert s.texts() == want_texts[j], j
+    for j, s in enumerate(sessions):
+        for slot, k in enumerate([k for k in range(n) if k != j], start=1):
+            assert (s.partner(slot, want_texts[k]) == -1).all(), (j, k)
+        if j == n - 1:
+            fields, rej = s.finish_b64(j == 0)
+            assert not rej.any() and s.split_fields(fields) == want_fields[j]
+        else:
+            w, u = s.finish(j == 0)
+            assert np.array_equal(w, want_wu[j][0]) and np.array_equal(u, want_wu[j][1]), j
+        s.close()
+    if n != 2:
+        return
+    dins = [tuple(dev(x) for x in a) for a in arrays]
+    sessions = [env.ctx.parties_begin_dev(dins[j][0], 32, dins[j][1], dins[j][2], woff, n, want_yrv=True)
+                for j in range(n)]
+    texts = [s.text_dev() for s in sessions]
+    bads, fields = [], []
+    for j, s in enumerate(sessions):
+        for slot, k in enumerate([k for k in range(n) if k != j], start=1):
+            bads.append(s.partner(slot, texts[k][0], texts[k][2]))
+        fields.append(s.finish_b64(j == 0))
+    torch.cuda.synchronize()
+    assert all((host(b) == NF).all() for b in bads)
+    for j, s in enumerate(sessions):
+        assert s.texts() == want_texts[j], j
+        assert FC.ints(host(s.y)) == ins[j][0] and FC.ints(host(s.r)) == ins[j][1] and FC.ints(host(s.v)) == ins[j][2]
+        assert s.split_fields([host(f) for f in fields[j]]) == want_fields[j], j
+        s.close()
+
+
+# ---- the client session: one party at a time into running sums (k_acc_b64, k_mask_sums, K_RV at n = 1) ----
+@pytest.mark.parametrize("n", FC.PARTY_COUNTS)
+def test_client_session(env, n):
+    """The rows of test_recombine_verify as base64 texts, accumulated forward,
+    in reverse and in one fixed permutation.  On the three BIG primes the
+    read-modify-write add carries past 2^128; on all eight a running sum lands
+    exactly on p and on p - 1, and the first and the last party to arrive bring
+    words >= p in every field (asserted on the inputs below).  Host mode runs
+    all three orders, device mode the permutation only: with three orders in
+    both modes a parameter took 0.03-0.06 s at 3-5 parties against the 0.01-0.02 s
+    of test_wire_fused's on the same rows, more than the twice it may."""
+    pr = env.pr
+    rows, odos, oy = env.rv(n)
+    W = rows.W
+    orders = FC.session_orders(n)
+    covs = [FC.assert_session_coverage(pr, rows, order) for order in orders]
+    cols = (rows.ys, rows.rs, rows.vs, rows.ws, rows.us)
+    secrets = env.secrets(W)
+    sec = FC.arr(secrets)
+    om, off = env.F.mask_input(sec, odos)
+    assert off == -1 and FC.ints(om) == FC.mask_words(pr, secrets, rows.ys)
+    records = b"".join(base64.b64encode(w.tobytes()) for w in om)
+    S = W - 193  # a verify-only tail longer than one 192-word tile
+    assert 0 < S
+    texts = texts_of(odos)
+    by_mode = {"host": (texts, sec), "device": (dev_texts(texts), dev(sec))}
+    h = lambda x: x if isinstance(x, (np.ndarray, bytes)) else host(x)  # noqa: E731
+
+    def fed(mode, tx, order):
+        s = env.ctx.client_begin(W, n) if mode == "host" else env.ctx.client_begin_dev(W, n)
+        assert [verdict(s.party(j, tx[j])) for j in order] == [-1] * n
+        return s
+
+    sums = FC.running_sums(pr, rows, orders[0])  # (a sum mod p: tests/test_session_cases_cpu.py holds every order to it)
+    for q, (order, cov) in enumerate(zip(orders, covs)):
+        picks = {0, W - 1}
+        if n >= 2:
+            picks.add(cov["exact_p_at"])
+        if pr.big and n >= 2:
+            picks.add(cov["carry_at"])
+        # host mode in every order; device mode launches the same kernels and takes the fixed permutation alone
+        for mode in ("host", "device") if order == orders[-1] else ("host",):
+            tx, sc = by_mode[mode]
+            tag = (mode, order)
+            with fed(mode, tx, order) as s:
+                y, ff, bad = s.finish_verify()
+                assert verdict(ff) == -1 and verdict(bad) == -1 and np.array_equal(h(y), oy), tag
+                for i in sorted(picks):
+                    want = tuple(col[i] for col in cols)
+                    assert want == tuple(FC.from_gfp(pr, sums[k][i]) for k in range(5))
+                    assert s.word(i) == want, (tag, i)
+            with fed(mode, tx, order) as s:
+                m16, rec, ff, bad = s.finish_mask(sc, records=True, raw=True)
+                assert verdict(ff) == -1 and verdict(bad) == -1 and np.array_equal(h(m16), om), tag
+                assert h(rec).tobytes() == records, tag
+            with fed(mode, tx, order) as s:
+                text, ff, bad = s.finish_mask_json(sc)
+                assert verdict(ff) == -1 and verdict(bad) == -1, tag
+                assert (text if mode == "host" else host(text).tobytes()) == data_text(om), tag
+            if q == 0 or mode == "device":  # fewer secrets than masks: the shorter output, every mask verified (below)
+                with fed(mode, tx, order) as s:
+                    m16, rec, ff, bad = s.finish_mask(sc[:S], records=True, raw=True)
+                    assert verdict(ff) == -1 and np.array_equal(h(m16), om[:S]), tag
+                    assert h(rec).tobytes() == records[:24 * S], tag
+    for q, at in enumerate(FC.fault_positions(W)):  # W - 1 and W // 2 lie in the verify-only tail of `S` secrets
+        order = orders[q % len(orders)]
+        bt = texts_of(FC.with_fault(odos, at))
+        for mode, tx, sc in (("host", bt, sec), ("device", dev_texts(bt), by_mode["device"][1])):
+            with fed(mode, tx, order) as s:
+                y, ff, bad = s.finish_verify()
+                assert verdict(ff) == at and verdict(bad) == -1, (mode, at)
+            with fed(mode, tx, order) as s:
+                assert verdict(s.finish_mask(sc[:S])[2]) == at, (mode, at)
+            with fed(mode, tx, order) as s:
+                assert verdict(s.finish_mask_json(sc)[1]) == at, (mode, at)
+
+
+# ---- many objects straight from their base64 texts (k_rv_b64_seg, k_mask_b64_seg, k_mask_json_seg) --------
+def slotted(texts_by_object, sizes, slot_chars):
+    """(text offsets, per party the five field buffers): object o's own text at
+    the sum of its predecessors' slots, '!' everywhere else."""
+    toff = np.concatenate([[0], np.cumsum([slot_chars(w) for w in sizes])]).astype(np.uint64)
+    n = len(texts_by_object[0])
+    bufs = [[np.full(int(toff[-1]), ord("!"), np.uint8) for _ in range(5)] for _ in range(n)]
+    for o, obj in enumerate(texts_by_object):
+        for j in range(n):
+            for k in range(5):
+                t = np.frombuffer(obj[j][k], np.uint8)
+                bufs[j][k][int(toff[o]):int(toff[o]) + t.size] = t
+    return toff[:-1].copy(), bufs
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5])  # every templated form and the run-time loop, BIG and !BIG
+def test_wire_packed(env, n):
+    """test_packed's objects, each object's fields encoded on their own (all
+    three base64 paddings occur); a fault in the first and in the last
+    object; one verdict per object."""
+    import amphora_amd
+    import torch
+    pr = env.pr
+    rows, odos, oy = env.rv(n)
+    FC.rv_coverage(pr, rows)
+    W = rows.W
+    secrets = env.secrets(W)
+    sec = FC.arr(secrets)
+    om, _ = env.F.mask_input(sec, odos)
+    assert FC.ints(om) == FC.mask_words(pr, secrets, rows.ys)
+    records = np.frombuffer(b"".join(base64.b64encode(w.tobytes()) for w in om), np.uint8).reshape(W, 24)
+    woff = np.array([0, 1, 130, W // 2 + 3, W - 2, W], np.uint64)
+    cuts = [(int(a), int(b)) for a, b in zip(woff, woff[1:])]
+    K = len(cuts)
+    assert {(16 * (b - a)) % 3 for a, b in cuts} == {0, 1, 2}  # "", "==" and "=" at the texts' ends
+    clean = [-1] * K
+    bad = FC.with_fault(FC.with_fault(odos, 0), W - 1)
+    faulty = [0, -1, -1, -1, 1]
+    for k, (lo, hi) in enumerate(cuts):  # the reference's per-object verdicts: each object verified on its own
+        _, off = env.F.recombine_verify([tuple(f[lo:hi] for f in o) for o in bad])
+        assert off == faulty[k]
+        assert FC.recombine_verify(pr, [tuple(FC.ints(f[lo:hi]) for f in o) for o in bad])[1] == faulty[k]
+    want_texts = [data_text(om[lo:hi]) for lo, hi in cuts]
+
+    def many(ff):
+        if not isinstance(ff, np.ndarray):
+            torch.cuda.synchronize()
+            ff = host(ff)
+        return [-1 if int(v) == NF else int(v) for v in ff]
+
+    for arrays, want in ((odos, clean), (bad, faulty)):
+        objs = [[[base64.b64encode(f[lo:hi].tobytes()) for f in o] for o in arrays] for lo, hi in cuts]
+        toff, bufs = slotted(objs, [hi - lo for lo, hi in cuts], amphora_amd._lib.wire_slot_chars)
+        for mode in ("host", "device"):
+            d = (lambda a: a) if mode == "host" else dev
+            g = (lambda a: a) if mode == "host" else host
+            tx = [[d(f) for f in o] for o in bufs]
+            wo, to = (woff, toff) if mode == "host" else (dev(woff.view(np.int64)), dev(toff.view(np.int64)))
+            y, ff, bc = env.ctx.recombine_verify_b64_packed(tx, wo, to)
+            assert many(ff) == want and many(bc) == clean and np.array_equal(g(y), oy), mode
+            m16, rec, ff, bc = env.ctx.mask_input_b64_packed(tx, wo, to, d(sec), records=True, raw=True)
+            assert many(ff) == want and many(bc) == clean, mode
+            assert np.array_equal(g(m16), om) and np.array_equal(g(rec), records), mode
+            text, oo, ff, bc = env.ctx.mask_input_json_packed(tx, wo, to, d(sec))
+            assert many(ff) == want and many(bc) == clean, mode
+            text, oo = g(text), g(oo)
+            for o in range(K):
+                got = text[int(oo[o]):int(oo[o]) + len(want_texts[o])].tobytes()
+                assert got == want_texts[o], (mode, o)
+
+
+# ---- many uploads in one launch (k_conv_json_seg) ------------------------------------------------------
+@pytest.mark.parametrize("zero", [False, True])
+def test_convert_share_json_packed(env, zero):
+    """test_convert_share's words as objects of 1, 127, 1 and the rest: both
+    sides of the 128-record tile, every object with its own "data" text at
+    its own alignment in one buffer."""
+    import torch
+    pr = env.pr
+    E = FC.edge_words(pr.p)
+    L = len(E)
+    W = L * L
+    masked = [E[i // L] for i in range(W)]
+    tuples = [(E[i % L], E[(i // L + 2 * i + 1) % L]) for i in range(W)]
+    for col in (masked, [t[0] for t in tuples], [t[1] for t in tuples]):
+        FC.assert_noncanonical(pr, col)
+    m16 = FC.arr(masked)
+    tup = FC.arr([x for t in tuples for x in t], 32)
+    woff = np.array([0, 1, 128, 129, W], np.uint64)
+    cuts = [(int(a), int(b)) for a, b in zip(woff, woff[1:])]
+    own = [data_text(m16[lo:hi]) for lo, hi in cuts]
+    buf = b"!".join(own)  # one foreign byte between the texts, which so start at offsets 0, 7, 4 and 11 mod 16
+    toff = np.array([sum(len(t) + 1 for t in own[:o]) for o in range(len(own))], np.uint64)
+    assert len({int(t) % 16 for t in toff}) >= 3
+    dbuf = dev(np.frombuffer(buf, np.uint8).copy())
+    for key in (0, 1, pr.p - 1, FC.UNIFORM_WORDS[0] % pr.p):
+        exp = env.F.convert_share(m16, tup, key, zero)
+        for lo, hi in cuts:  # Python ints on each object alone
+            assert FC.ints(exp[lo:hi]) == [x for t in FC.convert_share(pr, masked[lo:hi], tuples[lo:hi], key, zero)
+                                           for x in t], (key, lo)
+        out, bad = env.ctx.convert_share_json_packed(buf, woff, toff, tup, key, zero)
+        assert bad.tolist() == [-1] * len(cuts) and np.array_equal(out, exp), key
+        out, bad = env.ctx.convert_share_json_packed(dbuf, woff, toff, dev(tup), key, zero)
+        torch.cuda.synchronize()
+        assert host(bad).tolist() == [NF] * len(cuts) and np.array_equal(host(out), exp), key
+        outs, bad = env.ctx.convert_share_json_batch(own, [tup[lo:hi] for lo, hi in cuts], key, zero)
+        assert bad.tolist() == [-1] * len(cuts), key
+        assert all(np.array_equal(o, exp[lo:hi]) for o, (lo, hi) in zip(outs, cuts)), key
 
 
 # ---- device synth ---------------------------------------------------------------------------------

@@ -1,4 +1,6 @@
-"""The verdict matrix: every verifying call of the C ABI, in every party-count
+"""The verdict matrix: every verifying call of the C ABI (every declaration
+with a `first_fail`: the table MATRIX of tests/verdict_cases.py, held against
+the headers by tests/test_session_cases_cpu.py), in every party-count
 form (templated 1-4, the run-time loop at 5 and 16) and both prime classes
 (`test` is BIG, `m89` is !BIG and has room for + k p), on the catalogue of
 tests/verdict_cases.py -- a fault in each of the five MAC fields is rejected at
@@ -11,7 +13,13 @@ Python ints through tests/verdict_cases.py (tests/test_verdict_cpu.py pins
 the catalogue itself); wire texts are Python's base64 of the edited arrays.
 No result is compared with another call of the library.  The outputs are
 compared whole for rejected inputs too: the headers promise that they are
-written whatever the verdict.
+written whatever the verdict.  The client session is the exception the header
+states: its host-mode finish calls write no output on a rejection (checked on
+pre-filled buffers), its device-mode ones write everything; its parties arrive
+in an order that rotates with the case, and for every rejected case
+amph_client_word at the failing word gives the five recombined values of the
+edited rows -- the numbers the reference's failure message is rendered from,
+which crossed and compensated MACs tell apart from a read of the wrong column.
 
 Single-object calls run 1,217 words (a 1,024-lane workgroup edge, six 192-word
 wire tiles and a 65-word tail, base64 padding present); the packed and batch
@@ -19,6 +27,7 @@ calls hold the whole catalogue in one launch, one 257-word object per case, so
 objects are not aligned with waves.
 """
 import base64
+import ctypes as C
 import functools
 import json
 import os
@@ -40,8 +49,10 @@ N_SECRETS_SHORT = 700  # mask_input with a verify-only tail of 517 words
 SMALL_SIZES = [1, 192]  # one word; one whole wire tile (no base64 padding)
 BATCH_WORDS = 256  # the host pipeline's batch in these tests
 DEFAULT_BATCH_WORDS = 4 << 20  # capi_internal.hpp
-SINGLE_CALLS = ["recombine_verify", "mask_input", "verify", "recombine_verify_b64", "mask_input_b64", "mask_input_json"]
-MANY_CALLS = ["packed", "batch", "wire_packed", "wire_batch"]
+SINGLE_CALLS = ["recombine_verify", "mask_input", "verify", "recombine_verify_b64", "mask_input_b64", "mask_input_json",
+                "client_verify", "client_mask", "client_mask_json"]
+MANY_CALLS = ["packed", "batch", "wire_packed", "wire_batch", "upload_packed", "upload_batch"]
+OK, E_VERIFY = 0, 1
 
 
 # ---- contexts -------------------------------------------------------------------------
@@ -320,6 +331,89 @@ def run_mask_input_json(pid, n):
                 assert text == data_text(R.want_rec(e)), (R.W, on_dev, c.name)
 
 
+# ---- the client session: the same texts, one party at a time ------------------------------------
+def arrival_order(n, q, case):
+    """Rotates with the case index: forward, reverse, the edited party first."""
+    fwd = list(range(n))
+    if q % 3 == 0:
+        return fwd
+    if q % 3 == 1:
+        return fwd[::-1]
+    first = case.edits[0][0]
+    return [first] + [j for j in fwd if j != first]
+
+
+def run_client(pid, n, finish):
+    """amph_client_finish_verify / _mask / _mask_json (`finish`) and their _dev
+    forms over sums accumulated in a rotating arrival order.  Device mode: the
+    outputs whole, for rejected cases too.  Host mode, through the C ABI with
+    pre-filled buffers: a rejected case leaves them as they were.  Every
+    rejected case: amph_client_word at the failing word gives the five
+    recombined values of the edited rows -- what the failure message shows;
+    for classes C and D at every edited word."""
+    import amphora_amd
+    lib = amphora_amd._lib.lib
+    R = rows(pid, n)
+    ctx = _ctx(pid)
+    W = R.W
+    orders = set()
+    for on_dev in (False, True):
+        for q, (c, e) in enumerate(R.cases):
+            order = arrival_order(n, q, c)
+            orders.add(tuple(order))
+            texts = R.device_texts(c) if on_dev else R.host_texts(c)
+            tag = ("device" if on_dev else "host", c.name, order)
+            s = ctx.client_begin_dev(W, n) if on_dev else ctx.client_begin(W, n)
+            try:
+                bads = [s.party(j, texts[j]) for j in order]
+                if on_dev:
+                    if finish == "verify":
+                        y, ff, bad = s.finish_verify()
+                        got, want = [down(y)], [R.want_y(e)]
+                    elif finish == "mask":
+                        m16, rec, ff, bad = s.finish_mask(R.dev_sec(), records=True, raw=True)
+                        got, want = [down(m16), down(rec)], [R.want_m(e), R.want_rec(e)]
+                    else:
+                        text, ff, bad = s.finish_mask_json(R.dev_sec())
+                        got, want = [down(text).tobytes()], [data_text(R.want_rec(e))]
+                    assert verdict(ff) == e.ff and verdict(bad) == -1, (tag, verdict(ff), e.ff)
+                    assert all(verdict(b) == -1 for b in bads), tag
+                    for g, w in zip(got, want):  # written whatever the verdict
+                        assert np.array_equal(g, w) if isinstance(w, np.ndarray) else g == w, tag
+                else:
+                    assert bads == [-1] * n, tag
+                    ff, bad = C.c_int64(-7), C.c_int64(-7)
+                    if finish == "verify":
+                        outs, want = [np.full((W, 16), 0xA5, np.uint8)], [R.want_y(e)]
+                        st = lib.amph_client_finish_verify(s._h, outs[0].ctypes.data, C.byref(ff), C.byref(bad))
+                    elif finish == "mask":
+                        outs = [np.full((W, 16), 0xA5, np.uint8), np.full((W, 24), 0xA5, np.uint8)]
+                        want = [R.want_m(e), R.want_rec(e)]
+                        st = lib.amph_client_finish_mask(s._h, R.sec.ctypes.data, W, outs[0].ctypes.data,
+                                                         outs[1].ctypes.data, C.byref(ff), C.byref(bad))
+                    else:
+                        cap = 37 * W + 1
+                        outs = [np.full(cap, 0xA5, np.uint8)]
+                        want = [np.frombuffer(data_text(R.want_rec(e)), np.uint8)]
+                        st = lib.amph_client_finish_mask_json(s._h, R.sec.ctypes.data, W, outs[0].ctypes.data, cap,
+                                                              C.byref(ff), C.byref(bad))
+                    assert (st, ff.value, bad.value) == (E_VERIFY if e.ff >= 0 else OK, e.ff, -1), (tag, st, ff.value)
+                    for g, w in zip(outs, want):
+                        if e.ff >= 0:
+                            assert (g == 0xA5).all(), tag  # host mode writes no output on an error
+                        else:
+                            assert g.shape == w.shape and np.array_equal(g, w), tag
+                at = ({e.ff} if e.ff >= 0 else set()) | ({ed[2] for ed in c.edits} if c.cls in "CD" else set())
+                if at:  # (the compensated MACs of class D are accepted: their edited words are read back as well)
+                    cols = VC.columns(R.b, c)
+                    for i in sorted(at):
+                        assert s.word(i) == tuple(cols[k][i] for k in range(5)), (tag, i)
+            finally:
+                s.close()
+    if n >= 3:
+        assert len(orders) >= 3  # forward, reverse and at least one "edited party first" that is neither
+
+
 # ---- many objects per launch: one object per case -------------------------------------------
 class Many:
     """The catalogue at 257 words as objects of one launch: an honest object,
@@ -481,10 +575,72 @@ def run_wire_batch(pid, n):
     assert texts == [data_text(r) for r in M.rec]
 
 
+def upload_texts(M):
+    """Each object's expected "data" array text, from Python ints: the masked
+    words of the catalogue (FC.mask_words), Python's base64 and the frame."""
+    out = []
+    for o in range(M.K):
+        words = FC.ints(M.m[o])
+        text = data_text(record_rows(FC.arr(words)))
+        assert decoded_records(text) == words and len(text) == 37 * len(words) + 1
+        out.append(text)
+    return out
+
+
+def run_upload_packed(pid, n):
+    """amph_mask_input_json_packed: one 257-word object per case."""
+    import amphora_amd
+    ctx = _ctx(pid)
+    M = many(pid, n, False)
+    want = upload_texts(M)
+    toff, bufs = wire_buffers(M, amphora_amd._lib.wire_slot_chars)
+    clean = [-1] * M.K
+    for on_dev in (False, True):
+        get = down if on_dev else (lambda a: a)
+        tx = [[up(f) for f in o] for o in bufs] if on_dev else bufs
+        wo, to = (up(M.woff), up(toff)) if on_dev else (M.woff, toff)
+        sec = up(M.packed_sec) if on_dev else M.packed_sec
+        text, oo, ff, bad = ctx.mask_input_json_packed(tx, wo, to, sec)
+        assert verdicts(ff) == M.ff and verdicts(bad) == clean, on_dev
+        text, oo = get(text), [int(x) for x in get(oo)]
+        assert oo == [o * amphora_amd._lib.upload_slot_chars(W_OBJECT) for o in range(M.K)], on_dev
+        for o in range(M.K):  # written whatever the object's verdict
+            assert text[oo[o]:oo[o] + len(want[o])].tobytes() == want[o], (on_dev, M.names[o])
+    # AMPH_F_ACCUMULATE over two passes: the element-wise minimum of two REFERENCE verdict lists
+    import torch
+    M2 = many(pid, n, False, shift=7)
+    both = [min([x for x in pair if x >= 0], default=-1) for pair in zip(M.ff, M2.ff)]
+    assert M2.sizes == M.sizes and both != M.ff and both != M2.ff
+    acc = torch.full((M.K,), NF, dtype=torch.int64, device="cuda")
+    seen = torch.full((M.K,), NF, dtype=torch.int64, device="cuda")
+    for MM in (M, M2):
+        t2, b2 = wire_buffers(MM, amphora_amd._lib.wire_slot_chars)
+        text, oo, _, _ = ctx.mask_input_json_packed([[up(f) for f in o] for o in b2], up(MM.woff), up(t2),
+                                                    up(MM.packed_sec), first_fail=acc, bad_char=seen, accumulate=True)
+        text, oo = down(text), [int(x) for x in down(oo)]
+        for o, w in enumerate(upload_texts(MM)):
+            assert text[oo[o]:oo[o] + len(w)].tobytes() == w, (MM.names[o], "accumulate")
+    assert verdicts(acc) == both and verdicts(seen) == clean
+
+
+def run_upload_batch(pid, n):
+    """amph_mask_input_json_batch: the same objects, gathered from their own host buffers."""
+    ctx = _ctx(pid)
+    M = many(pid, n, False)
+    texts, ff, bad = ctx.mask_input_json_batch(M.texts, M.sizes, M.secrets)
+    assert verdicts(ff) == M.ff and verdicts(bad) == [-1] * M.K
+    assert texts == upload_texts(M)
+
+
 RUN = {"recombine_verify": run_recombine_verify, "mask_input": run_mask_input, "verify": run_verify,
        "recombine_verify_b64": run_recombine_verify_b64, "mask_input_b64": run_mask_input_b64,
        "mask_input_json": run_mask_input_json, "packed": run_packed, "batch": run_batch,
-       "wire_packed": run_wire_packed, "wire_batch": run_wire_batch}
+       "wire_packed": run_wire_packed, "wire_batch": run_wire_batch,
+       "client_verify": functools.partial(run_client, finish="verify"),
+       "client_mask": functools.partial(run_client, finish="mask"),
+       "client_mask_json": functools.partial(run_client, finish="mask_json"),
+       "upload_packed": run_upload_packed, "upload_batch": run_upload_batch}
+assert list(RUN) and set(RUN) == set(VC.MATRIX.values()) == set(SINGLE_CALLS + MANY_CALLS)
 
 
 @pytest.mark.parametrize("call", SINGLE_CALLS + MANY_CALLS)

@@ -1,6 +1,7 @@
 """The verdict catalogue: honest ODO rows and named sets of edits to them, with
 the verdict each one must get, shared by tests/test_verdict_cpu.py and
-tests/test_hip_verdicts.py.
+tests/test_hip_verdicts.py; and MATRIX, the calls the catalogue runs through
+(tests/test_session_cases_cpu.py holds it against the headers).
 
 Every verifying call ends in ``ok = (y r == w) & (v r == u)``.  The catalogue
 holds, for one prime, party count and word count,
@@ -37,7 +38,34 @@ TOP = FC.M128 - 1
 # with + 1 (limb 0) one bit in each 32-bit limb of the compare, and the top bit
 LIMB_DELTAS = (("d32", 1 << 32), ("d64", 1 << 64), ("d96", 1 << 96), ("top", 1 << 127))
 
-Base = namedtuple("Base", "pid n W odos cols")          # odos[party][field][i] raw words, cols[field][i] canonical
+# The verdict matrix: every ABI call that takes a `first_fail` (a *_dev sibling
+# through its base name) -> the `call` parameter of
+# tests/test_hip_verdicts.py::test_verdicts that runs the catalogue through it.
+# tests/test_session_cases_cpu.py holds this table against include/*.h.
+MATRIX = {
+    "amph_recombine_verify": "recombine_verify",
+    "amph_mask_input": "mask_input",
+    "amph_verify": "verify",
+    "amph_recombine_verify_b64": "recombine_verify_b64",
+    "amph_mask_input_b64": "mask_input_b64",
+    "amph_mask_input_json": "mask_input_json",
+    "amph_client_finish_verify": "client_verify",
+    "amph_client_finish_mask": "client_mask",
+    "amph_client_finish_mask_json": "client_mask_json",
+    "amph_recombine_verify_packed": "packed",
+    "amph_mask_input_packed": "packed",
+    "amph_recombine_verify_batch": "batch",
+    "amph_mask_input_batch": "batch",
+    "amph_recombine_verify_b64_packed": "wire_packed",
+    "amph_mask_input_b64_packed": "wire_packed",
+    "amph_recombine_verify_b64_batch": "wire_batch",
+    "amph_mask_input_b64_batch": "wire_batch",
+    "amph_mask_input_json_packed": "upload_packed",
+    "amph_mask_input_json_batch": "upload_batch",
+}
+MATRIX_LEFT_OUT = {}  # {ABI symbol with a first_fail: why the matrix does not run it}
+
+Base = namedtuple("Base", "pid n W odos cols")         # odos[party][field][i] raw words, cols[field][i] canonical
 Case = namedtuple("Case", "name cls edits want_ff y_changes limb")
 Expect = namedtuple("Expect", "ff changed")             # changed: {index: new canonical secret}
 
