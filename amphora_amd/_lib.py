@@ -200,6 +200,29 @@ def _load():
     L.amph_client_parties_seen.argtypes = [vp]
     L.amph_client_free.restype = None
     L.amph_client_free.argtypes = [vp]
+    # include/amphora_client_batch.h
+    L.amph_clients_begin.argtypes = [vp, vp, sz, i32, pp]
+    L.amph_clients_begin_dev.argtypes = [vp, vp, sz, i32, vp, pp]
+    for f in (L.amph_clients_objects, L.amph_clients_words, L.amph_clients_field_chars,
+              L.amph_clients_upload_chars):
+        f.restype = sz
+        f.argtypes = [vp]
+    L.amph_clients_parties_seen.argtypes = [vp]
+    L.amph_clients_field_offsets.argtypes = [vp, vp]
+    L.amph_clients_upload_offsets.argtypes = [vp, vp]
+    L.amph_clients_party.argtypes = [vp, i32, vp, vp]
+    L.amph_clients_party_dev.argtypes = [vp, i32, vp, vp, vp]
+    L.amph_clients_finish_verify.argtypes = [vp, vp, vp, vp]
+    L.amph_clients_finish_verify_dev.argtypes = [vp, vp, vp, vp, vp]
+    L.amph_clients_finish_mask.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.amph_clients_finish_mask_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.amph_clients_finish_mask_json.argtypes = [vp, vp, vp, sz, vp, vp]
+    L.amph_clients_finish_mask_json_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    L.amph_clients_word.argtypes = [vp, sz, sz, vp]
+    L.amph_clients_copies.restype = u64
+    L.amph_clients_copies.argtypes = [vp]
+    L.amph_clients_free.restype = None
+    L.amph_clients_free.argtypes = [vp]
     return L
 
 
@@ -278,6 +301,15 @@ EXPORTED_CLIENT_SESSION = ["amph_client_begin", "amph_client_party", "amph_clien
                            "amph_client_words", "amph_client_parties_seen", "amph_client_free",
                            "amph_client_begin_dev", "amph_client_party_dev", "amph_client_finish_verify_dev",
                            "amph_client_finish_mask_dev", "amph_client_finish_mask_json_dev"]
+# what include/amphora_client_batch.h declares
+EXPORTED_CLIENTS_SESSION = ["amph_clients_begin", "amph_clients_begin_dev", "amph_clients_objects",
+                            "amph_clients_words", "amph_clients_parties_seen", "amph_clients_field_chars",
+                            "amph_clients_upload_chars", "amph_clients_field_offsets",
+                            "amph_clients_upload_offsets", "amph_clients_party", "amph_clients_party_dev",
+                            "amph_clients_finish_verify", "amph_clients_finish_verify_dev",
+                            "amph_clients_finish_mask", "amph_clients_finish_mask_dev",
+                            "amph_clients_finish_mask_json", "amph_clients_finish_mask_json_dev",
+                            "amph_clients_word", "amph_clients_copies", "amph_clients_free"]
 ODO_FIELD_NAMES = ("secretShares", "rShares", "vShares", "wShares", "uShares")
 
 
@@ -1542,6 +1574,37 @@ class Context:
         self._check(lib.amph_client_begin_dev(self._h, words, n_parties, C.c_void_p(stream.cuda_stream), C.byref(h)))
         return ClientSession(self, h, words, n_parties, stream)
 
+    # -- the client side as a session for K secrets (include/amphora_client_batch.h) --
+    def clients_begin(self, word_offsets, n_parties: int) -> "ClientSessions":
+        """amph_clients_begin: a host-mode session for K secrets (secret o =
+        words [word_offsets[o], word_offsets[o + 1])) that takes each party's
+        five slotted field buffers as they arrive (ClientSessions.party /
+        party_texts) and finishes from the running sums, a verdict per secret."""
+        wo = np.ascontiguousarray(word_offsets, dtype=np.uint64)
+        _need(wo.ndim == 1 and wo.size >= 1, "word_offsets: one entry per object and the total")
+        h = C.c_void_p()
+        self._check(lib.amph_clients_begin(self._h, _ptr(wo), wo.size - 1, n_parties, C.byref(h)))
+        return ClientSessions(self, h, wo, n_parties, None)
+
+    def clients_begin_dev(self, word_offsets, n_parties: int, stream=None) -> "ClientSessions":
+        """amph_clients_begin_dev: word_offsets is a host array; texts,
+        secrets, outputs and verdict arrays are torch device tensors, every
+        call asynchronous on the ONE stream of the session (`stream`: a torch
+        stream; torch's current stream when None)."""
+        import torch
+        wo = np.ascontiguousarray(word_offsets, dtype=np.uint64)
+        _need(wo.ndim == 1 and wo.size >= 1, "word_offsets: one entry per object and the total")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        h = C.c_void_p()
+        self._check(lib.amph_clients_begin_dev(self._h, _ptr(wo), wo.size - 1, n_parties,
+                                               C.c_void_p(stream.cuda_stream), C.byref(h)))
+        return ClientSessions(self, h, wo, n_parties, stream)
+
+    def clients_copies(self) -> int:
+        """amph_clients_copies: host-device copies of the host-mode ClientSessions calls."""
+        return int(lib.amph_clients_copies(self._h))
+
     # -- synthetic device inputs (bench / tests) --------------------------------
     def synth_odos(self, seed: int, n: int, words: int, fault_index: int = -1,
                    noncanon_permille: int = 0, with_plain: bool = False, buf=None):
@@ -1761,6 +1824,209 @@ class ClientSession:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             lib.amph_client_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        if lib is not None:
+            self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ClientSessions:
+    """One amph_clients (include/amphora_client_batch.h): K secrets in one
+    client session.  Each party's K responses arrive as five slotted field
+    buffers (object o's text at field_offsets[o] of each, the layout
+    PartySessions.finish_b64 writes) and are added into running sums in one
+    launch; the finish calls give, per object, what the packed wire-text calls
+    give on all parties' buffers.  Host mode takes uint8 arrays / bytes and
+    returns numpy arrays with -1 for a clean verdict; device mode
+    (Context.clients_begin_dev) takes and returns torch device tensors with
+    AMPH_NO_FAILURE for a clean verdict, asynchronous on the session's stream."""
+
+    def __init__(self, ctx: Context, h, word_offsets, n_parties: int, stream):
+        self.ctx, self._h, self.n, self.stream = ctx, h, n_parties, stream
+        self.word_offsets = word_offsets
+        self.objects, self.words = int(word_offsets.size - 1), int(word_offsets[-1])
+        self.field_chars = int(lib.amph_clients_field_chars(h))
+        self.upload_chars = int(lib.amph_clients_upload_chars(h))
+        self.field_offsets = np.empty(self.objects, np.uint64)
+        self.upload_offsets = np.empty(self.objects, np.uint64)
+        Context._check(lib.amph_clients_field_offsets(h, _ptr(self.field_offsets)))
+        Context._check(lib.amph_clients_upload_offsets(h, _ptr(self.upload_offsets)))
+
+    @property
+    def dev(self) -> bool:
+        return self.stream is not None
+
+    def _sp(self):
+        return C.c_void_p(self.stream.cuda_stream)
+
+    def _array(self, shape, dtype="uint8"):
+        if self.dev:
+            import torch
+            return torch.empty(shape, dtype=getattr(torch, dtype), device="cuda:%d" % self.ctx.device)
+        return np.empty(shape, dtype=dtype)
+
+    @property
+    def parties_seen(self) -> int:
+        return int(lib.amph_clients_parties_seen(self._h))
+
+    def object_words(self, o: int) -> int:
+        return int(self.word_offsets[o + 1] - self.word_offsets[o])
+
+    def field_lens(self):
+        return [wire_text_chars(self.object_words(o)) for o in range(self.objects)]
+
+    def pack_texts(self, texts_by_object):
+        """K x 5 strings (texts_by_object[o][k]: object o's field k, ODO order)
+        -> the five slotted buffers (uint8 arrays of field_chars characters;
+        what lies between the texts is 0).  A text of another length than its
+        object's raises AmphoraNativeError(AMPH_E_LEN)."""
+        _need(len(texts_by_object) == self.objects,
+              "expected %d objects' texts, got %d" % (self.objects, len(texts_by_object)))
+        bufs = np.zeros((5, max(self.field_chars, 1)), np.uint8)
+        for o, (five, nc) in enumerate(zip(texts_by_object, self.field_lens())):
+            _need(len(five) == 5, "object %d: five base64 fields" % o)
+            at = int(self.field_offsets[o])
+            for k, t in enumerate(five):
+                if isinstance(t, str):
+                    t = t.encode("ascii", errors="replace")
+                a = np.frombuffer(bytes(t), np.uint8)
+                if a.size != nc:
+                    raise AmphoraNativeError(AMPH_E_LEN, "object %d: base64 fields of %d characters, expected %d "
+                                                         "for %d words" % (o, a.size, nc, self.object_words(o)))
+                bufs[k, at:at + nc] = a
+        return [bufs[k, :self.field_chars] for k in range(5)]
+
+    def party(self, slot: int, five_buffers, bad=None, status: bool = False):
+        """Party `slot`'s five slotted field buffers (ODO order) into the sums:
+        one launch whatever K is.  Host: -> this call's bad_chars[K] (-1
+        clean); raises ValueError with the packed calls' message when any
+        object holds an illegal character, unless status (then -> (bad_chars,
+        (status, message))); the slot counts as taken either way.  Device:
+        the buffers of a PartySessionsDev.finish_b64 go in unchanged; -> the
+        int64 (K,) verdict tensor (`bad`, or a new one)."""
+        if self.dev and any(b is None for b in five_buffers):  # (a session of empty objects only)
+            five_buffers = [self._array((0,)) for _ in range(5)]
+        arr, keep = self.ctx._text_structs([five_buffers])
+        if self.dev:
+            if not all(_is_dev(k) for k in keep):
+                raise ValueError("a device-mode session takes device tensors")
+            if bad is None:
+                bad = self._array((self.objects,), "int64")
+            Context._check(lib.amph_clients_party_dev(self._h, slot, arr, _ptr(bad), self._sp()))
+            return bad
+        if any(_is_dev(k) for k in keep):
+            raise ValueError("a host-mode session takes host buffers")
+        v = np.full(self.objects, -1, np.int64)
+        st = lib.amph_clients_party(self._h, slot, arr, _ptr(v))
+        msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
+        if st == AMPH_E_PARAM and (v >= 0).any():
+            if status:
+                return v, (st, msg)
+            raise ValueError(msg)
+        Context._check(st)
+        return (v, (st, msg)) if status else v
+
+    def party_texts(self, slot: int, texts_by_object, status: bool = False):
+        """party() on K x 5 host strings, gathered into the slotted buffers."""
+        bufs = self.pack_texts(texts_by_object)
+        if self.dev:
+            import torch
+            with torch.cuda.stream(self.stream):  # the upload is ordered before the launch that reads it
+                bufs = [torch.from_numpy(np.ascontiguousarray(b)).to("cuda:%d" % self.ctx.device) for b in bufs]
+            return self.party(slot, bufs)
+        return self.party(slot, bufs, status=status)
+
+    def _verdicts(self):
+        """(first_fails, bad_chars): host arrays start at -1, so a call that is
+        refused before it writes them reports no verdict."""
+        if self.dev:
+            return self._array((self.objects,), "int64"), self._array((self.objects,), "int64")
+        return np.full(self.objects, -1, np.int64), np.full(self.objects, -1, np.int64)
+
+    def _done(self, st, res, bad, status):
+        """Per-object verdicts are the result: AMPH_E_VERIFY, and AMPH_E_PARAM
+        with a bad character reported in bad_chars, return them (status=True
+        appends (status, amph_last_error)); anything else raises."""
+        msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
+        if not (st == AMPH_E_PARAM and not self.dev and (bad >= 0).any()):
+            Context._check(st, allow_verify=True)
+        return res + ((st, msg),) if status else res
+
+    def finish_verify(self, status: bool = False):
+        """-> (canonical secrets (T, 16) packed on word_offsets, first_fails[K],
+        bad_chars[K]), as Context.recombine_verify_b64_packed."""
+        out = self._array((self.words, 16))
+        ff, bad = self._verdicts()
+        if self.dev:
+            st = lib.amph_clients_finish_verify_dev(self._h, _ptr(out), _ptr(ff), _ptr(bad), self._sp())
+        else:
+            st = lib.amph_clients_finish_verify(self._h, _ptr(out), _ptr(ff), _ptr(bad))
+        return self._done(st, (out, ff, bad), bad, status)
+
+    def _secrets(self, secrets16):
+        sv = words_view(secrets16)
+        if _is_dev(sv) != self.dev:
+            raise ValueError("secrets must live where the session's texts live")
+        _need(sv.shape[0] == self.words, "one secret per input mask word: expected %d, got %d" % (
+            self.words, sv.shape[0]))
+        return sv
+
+    def finish_mask(self, secrets16, records: bool = True, raw: bool = False, status: bool = False):
+        """-> (masked (T, 16) or None, records (T, 24) or None, first_fails[K],
+        bad_chars[K]), as Context.mask_input_b64_packed."""
+        sv = self._secrets(secrets16)
+        o16 = self._array((self.words, 16)) if raw else None
+        o24 = self._array((self.words, 24)) if records else None
+        ff, bad = self._verdicts()
+        if self.dev:
+            st = lib.amph_clients_finish_mask_dev(self._h, _ptr(sv), _ptr(o16), _ptr(o24), _ptr(ff), _ptr(bad),
+                                                  self._sp())
+        else:
+            st = lib.amph_clients_finish_mask(self._h, _ptr(sv), _ptr(o16), _ptr(o24), _ptr(ff), _ptr(bad))
+        return self._done(st, (o16, o24, ff, bad), bad, status)
+
+    def finish_mask_json(self, secrets16, out=None, status: bool = False):
+        """-> (the framed texts: one uint8 buffer of upload_chars characters
+        with object o's "data" array text at upload_offsets[o], first_fails[K],
+        bad_chars[K]), as Context.mask_input_json_packed; the buffer goes into
+        Context.convert_share_json_packed unchanged.  `out`: write into the
+        caller's buffer (what lies between the texts stays as it is)."""
+        sv = self._secrets(secrets16)
+        if out is None:
+            out = self._array((max(self.upload_chars, 1),))
+            out[:] = 0
+        cap = int(out.numel() if self.dev else out.size)
+        ff, bad = self._verdicts()
+        if self.dev:
+            st = lib.amph_clients_finish_mask_json_dev(self._h, _ptr(sv), _ptr(out), cap, _ptr(ff), _ptr(bad),
+                                                       self._sp())
+        else:
+            st = lib.amph_clients_finish_mask_json(self._h, _ptr(sv), _ptr(out), cap, _ptr(ff), _ptr(bad))
+        return self._done(st, (out, ff, bad), bad, status)
+
+    def split_upload(self, text):
+        """finish_mask_json's buffer (host) -> the K framed texts (bytes)."""
+        return [bytes(text[int(a):int(a) + masked_input_data_chars(self.object_words(o))])
+                for o, a in enumerate(self.upload_offsets)]
+
+    def word(self, o: int, i: int):
+        """amph_clients_word: the recombined (y, r, v, w, u) of word i of object o as ints."""
+        out = np.empty((5, 16), np.uint8)
+        Context._check(lib.amph_clients_word(self._h, o, i, _ptr(out)))
+        return tuple(int.from_bytes(out[k].tobytes(), "little") for k in range(5))
+
+    def close(self):
+        # (a session finalised after its context -- the collector's order in a
+        # reference cycle is arbitrary -- must not touch the destroyed context)
+        if getattr(self, "_h", None) is not None and self._h.value and getattr(self.ctx, "_h", None) is not None:
+            lib.amph_clients_free(self._h)
         self._h = None
 
     def __del__(self):

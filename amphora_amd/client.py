@@ -584,6 +584,148 @@ class ResponseSession:
         self.close()
 
 
+class ResponseSessions:
+    """ResponseSession for K secrets (include/amphora_client_batch.h): every
+    party hands in its K response bodies at once (add_bodies: their 5 K base64
+    member strings are gathered into five slotted buffers and added into the
+    running sums in ONE launch; any thread may hand in its own party), and
+    secrets / masked_input_bodies finish from the sums -- one entry per
+    secret, the value or that secret's exception, as verify_vss_json_batch /
+    create_masked_input_bodies return on the same bodies.  The first party's K
+    bodies fix the word table; only party 0's bodies are kept as text (their
+    tags)."""
+
+    def __init__(self, util: SecretShareUtil, n_parties: int):
+        import threading
+        self._util, self._n = util, n_parties
+        self._lock = threading.Lock()
+        self._session = None
+        self._words = None   # per object, fixed by the first party that arrives
+        self._bodies0 = None
+        self._errors = None  # per object: the first malformed body's exception
+
+    @property
+    def words(self):
+        return self._words
+
+    def _begin(self, texts):
+        from . import wire
+        words, errors = [], []
+        for t in texts:
+            try:
+                words.append(wire.words_of_b64(len(t[0]), t[0][-2:]))
+                errors.append(None)
+            except ValueError as e:  # not whole words: this secret alone fails
+                words.append(0)
+                errors.append(AmphoraClientException(str(e)))
+        self._words, self._errors = words, errors
+        self._session = self._util.context.clients_begin(np.concatenate([[0], np.cumsum(words)]).astype(np.uint64),
+                                                         self._n)
+
+    def add_bodies(self, party_index: int, bodies) -> None:
+        """Party `party_index`'s K bodies (one per secret, in the order of the
+        first party's).  A malformed body or a bad character fails its own
+        secret only; the finish reports it."""
+        from . import wire
+        texts = [wire.odo_field_texts(b)[0] for b in bodies]
+        if party_index == 0:
+            self._bodies0 = list(bodies)
+        with self._lock:
+            if self._session is None:
+                self._begin(texts)
+            if len(texts) != len(self._words):
+                raise AmphoraClientException("party %d answered %d of %d secrets" % (
+                    party_index, len(texts), len(self._words)))
+            s = self._session
+            bufs = np.zeros((5, max(s.field_chars, 1)), np.uint8)
+            for o, (t, nc) in enumerate(zip(texts, s.field_lens())):
+                if self._errors[o] is not None:
+                    continue
+                if any(len(f) != nc for f in t):  # its slot stays 0: an illegal character in this object alone
+                    self._errors[o] = AmphoraClientException("The provided shares must be of the same length")
+                    continue
+                at = int(s.field_offsets[o])
+                for k in range(5):
+                    f = t[k].encode("ascii", errors="replace") if isinstance(t[k], str) else bytes(t[k])
+                    bufs[k, at:at + nc] = np.frombuffer(f, np.uint8)
+        s.party(party_index, [bufs[k, :s.field_chars] for k in range(5)], status=True)
+
+    def _outcomes(self, ff, bad, value):
+        out = []
+        for o, W in enumerate(self._words):
+            if self._errors[o] is not None:
+                out.append(self._errors[o])
+            elif bad[o] >= 0:
+                out.append(AmphoraClientException(_lib.wire_bad_char_message(int(bad[o]), W)))
+            elif ff[o] >= 0:
+                y, r, v, w, u = self._session.word(o, int(ff[o]))
+                out.append(IntegrityVerificationException(self._util.failure_message(y, r, u, v, w)))
+            else:
+                out.append(_outcome(value, o))
+        return out
+
+    def _need_session(self):
+        if self._session is None:
+            raise AmphoraClientException("no response body was added")
+        return self._session
+
+    def secrets(self, secret_ids=None):
+        """-> one entry per secret: (secretId, tags, canonical secrets) or the
+        exception verify_vss_json raises for it."""
+        from . import wire
+        s = self._need_session()
+        y, ff, bad = s.finish_verify()
+        wo = s.word_offsets
+
+        def value(o):
+            b0 = self._bodies0[o]
+            sid, tags = wire.vss_metadata(b0, wire.odo_field_texts(b0)[1])
+            return (sid if secret_ids is None else secret_ids[o]), tags, unpack(y[int(wo[o]):int(wo[o + 1])])
+
+        return self._outcomes(ff, bad, value)
+
+    def masked_input_bodies(self, secrets: Sequence[Secret]):
+        """-> one entry per secret: the MaskedInput JSON body or the exception
+        create_masked_input_body raises for it.  A secret with fewer words
+        than its masks is padded for the launch (every mask is verified) and
+        its text cut after its own last record; one with more is an
+        IndexError once its masks have verified, as in the single call."""
+        import json
+        from . import wire
+        s = self._need_session()
+        if len(secrets) != len(self._words):
+            raise ValueError("one secret per object of the session")
+        padded = np.zeros((s.words, 16), np.uint8)
+        for o, sec in enumerate(secrets):
+            W, a = self._words[o], int(s.word_offsets[o])
+            m = min(W, sec.size())
+            if m:
+                padded[a:a + m] = pack(sec.data[:m], self._util.prime)
+        text, ff, bad = s.finish_mask_json(padded)
+        framed = s.split_upload(text)
+
+        def value(o):
+            sec, W = secrets[o], self._words[o]
+            if sec.size() > W:
+                raise IndexError("Index %d out of bounds for length %d" % (W, W))
+            S = sec.size()
+            data = framed[o] if S == W else (framed[o][:37 * S] + b"]" if S else b"[]")
+            tj = json.dumps([wire._tag_obj(t) for t in sec.tags], separators=(",", ":"))
+            return '{"secretId":"%s","data":%s,"tags":%s}' % (sec.secret_id, data.decode("ascii"), tj)
+
+        return self._outcomes(ff, bad, value)
+
+    def close(self):
+        if self._session is not None:
+            self._session.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def get_secret_data(util: SecretShareUtil, odos: Sequence[OutputDeliveryObject]) -> List[int]:
     """getSecret :206-217 arithmetic (alias of verify_output_delivery_objects)."""
     return verify_output_delivery_objects(util, odos)

@@ -1,13 +1,14 @@
 // Internals shared by the units of the C ABI (capi_*.hip -- capi_ctx,
 // capi_pipeline, capi_words, capi_text, capi_party, parties_session,
-// client_session and capi_batch, the many-objects-per-call families): the context, the error and device
-// helpers, the word-array pipeline's types and the buffers of one-shot host
-// calls.  Everything here lives in one namespace of hidden
+// client_session, clients_session and capi_batch, the many-objects-per-call
+// families): the context, the error and device helpers, the word-array
+// pipeline's types, the buffers of one-shot host calls and the one host image
+// of the many-objects calls.  Everything here lives in one namespace of hidden
 // visibility: the library exports only what include/amphora.h and its
 // extension headers include/amphora_wire_batch.h,
 // include/amphora_upload_batch.h, include/amphora_respond_batch.h,
-// include/amphora_exchange_batch.h, include/amphora_party_batch.h and
-// include/amphora_client_session.h declare.
+// include/amphora_exchange_batch.h, include/amphora_party_batch.h,
+// include/amphora_client_session.h and include/amphora_client_batch.h declare.
 //
 // Host-pointer calls stream the word arrays through the device in batches
 // (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
@@ -40,8 +41,10 @@
 #include "../../include/amphora_exchange_batch.h"
 #include "../../include/amphora_party_batch.h"
 #include "../../include/amphora_client_session.h"
+#include "../../include/amphora_client_batch.h"
 #include "host_stream.hpp"
 #include "kernels.hpp"
+#include "wiretiles.hpp"
 
 namespace capi __attribute__((visibility("hidden"))) {
 using amph::Fp;
@@ -153,6 +156,7 @@ struct amph_ctx {
   std::atomic<uint64_t> upload_copies{0};  // the same of amphora_upload_batch.h's calls (amph_upload_batch_copies)
   std::atomic<uint64_t> respond_copies{0};  // and of amphora_respond_batch.h's (amph_respond_batch_copies)
   std::atomic<uint64_t> exchange_copies{0};  // and of amphora_exchange_batch.h's (amph_exchange_batch_copies)
+  std::atomic<uint64_t> clients_copies{0};  // and of amphora_client_batch.h's host-mode calls (amph_clients_copies)
   DevBuf xstage;  // host-mode staging of the exchange codec calls
   DevBuf xdev;    // device-mode scan scratch of the exchange codec calls
   hipEvent_t xdev_done = nullptr;  // the last device-mode exchange call's kernels
@@ -377,5 +381,136 @@ int check_parties(const amph_odo_b64* odos, int n);
 // AMPH_E_PARAM with the wire-text calls' message for a bad_char verdict,
 // (5 party + field) * nchars + offset
 int wire_bad_message(int64_t bad, size_t nchars);
+
+// The verdict words of a many-objects wire-text call (first-fail array, then
+// bad-character array, K words each) as the caller's entries and the call's
+// status: the packed calls of capi_batch.hip and the K-secret client session
+// (clients_session.hip) report alike.
+inline int wire_batch_status(const unsigned long long* v, size_t K, const uint64_t* woff, int64_t* first_fail,
+                             int64_t* bad_char) {
+  size_t nbad = 0, nfail = 0, fb = 0, ff = 0;
+  for (size_t o = 0; o < K; ++o) {
+    const bool bad = v[K + o] != amph::kNoFail, failed = !bad && v[o] != amph::kNoFail;
+    if (bad && !nbad++) fb = o;
+    if (failed && !nfail++) ff = o;
+    bad_char[o] = bad ? (int64_t)v[K + o] : -1;
+    first_fail[o] = failed ? (int64_t)v[o] : -1;
+  }
+  if (nbad) {
+    const size_t nc = amph::wire_text_chars(woff[fb + 1] - woff[fb]), f = (size_t)v[K + fb] / nc;
+    return fail(AMPH_E_PARAM, "object " + std::to_string(fb) + ": Illegal base64 character at index " +
+                                  std::to_string((size_t)v[K + fb] % nc) + " of party " + std::to_string(f / 5) +
+                                  "'s " + kOdoFieldNames[f % 5] + " (" + std::to_string(nbad) + " of " +
+                                  std::to_string(K) + " objects hold an illegal character)");
+  }
+  if (nfail)
+    return fail(AMPH_E_VERIFY, "Verification of secret has failed: object " + std::to_string(ff) + " at word " +
+                                   std::to_string(v[ff]) + " (" + std::to_string(nfail) + " of " +
+                                   std::to_string(K) + " objects failed)");
+  return AMPH_OK;
+}
+
+// ---- the host image of the many-objects calls -----------------------------------
+// Host mode of every call of capi_batch.hip and of the K-secret client
+// session moves ONE image to the device and one back, whatever the object
+// count, around ONE launch (the exchange codec's: one fixed sequence of
+// launches): 256-aligned regions, all the inputs (tables first) before all
+// the outputs, the verdict words last.
+//   Small (the image fits the small-call arena): it is built in the arena and
+// the kernel reads and writes it in place; the verdict words stay in device
+// memory (c->seg: atomics) while the kernel runs and come to the arena by a
+// copy kernel before the call's one synchronisation, as run_packed_small.
+// No host-device copy.
+//   Staged: the image is built in c->wire_img (page-locked) and mirrored in
+// c->wire; one blocking copy of the inputs while the stream is idle
+// (kPageableRule), one of the outputs and verdicts after the synchronisation,
+// each counted in the family's copy counter.
+// The context's mutex is held from open() to the image's end of life; a
+// caller that already holds it hands its lock over in `lock` before open().
+struct BatchImage {
+  amph_ctx* c = nullptr;
+  hipStream_t s = nullptr;
+  bool small = false;
+  size_t in_bytes = 0, total = 0;  // the inputs are [0, in_bytes), the outputs [in_bytes, total)
+  size_t verd = 0, n_verd = 0;     // the verdict words' offset and count
+  const char* verd_what = "";
+  uint8_t *himg = nullptr, *dimg = nullptr;
+  unsigned long long* dverd = nullptr;  // the verdict words the kernel writes
+  std::atomic<uint64_t>* copies = nullptr;
+  std::unique_lock<std::mutex> lock;
+
+  // Regions, in the image's order: every in() before the first out(), verdicts() last.
+  size_t in(size_t bytes) {
+    const size_t at = in_bytes;
+    total = in_bytes += align256(bytes);
+    return at;
+  }
+  size_t out(size_t bytes) {
+    const size_t at = total;
+    total += align256(bytes);
+    return at;
+  }
+  void verdicts(size_t words, const char* what) {
+    n_verd = words;
+    verd_what = what;
+    verd = out(8 * words);
+  }
+
+  // `family` names the staged buffers in an AMPH_E_NOMEM message
+  int open(amph_ctx* ctx, std::atomic<uint64_t> amph_ctx::*counter, const char* family) {
+    c = first_device(ctx);
+    copies = &(c->*counter);
+    if (!lock.owns_lock()) lock = std::unique_lock<std::mutex>(c->mu);
+    HIP_TRY(use_device(c->device));
+    if (int st = host_stream(c, 0, &s)) return st;
+    small = small_call(c, total);
+    if (small) {
+      if (c->small.ensure(total + 256) != hipSuccess) return fail(AMPH_E_NOMEM, "small-call arena");
+      if (n_verd && dev_ensure(c, c->seg, 8 * n_verd) != hipSuccess) return fail(AMPH_E_NOMEM, verd_what);
+      himg = dimg = (uint8_t*)c->small.p;
+      dverd = (unsigned long long*)c->seg.p;
+    } else {
+      if (c->wire_img.ensure(total) != hipSuccess) return fail(AMPH_E_NOMEM, std::string(family) + " batch image");
+      if (dev_ensure(c, c->wire, total) != hipSuccess) return fail(AMPH_E_NOMEM, std::string(family) + " staging");
+      himg = (uint8_t*)c->wire_img.p;
+      dimg = (uint8_t*)c->wire.p;
+      dverd = (unsigned long long*)(dimg + verd);
+    }
+    return AMPH_OK;
+  }
+  uint8_t* host(size_t off) const { return himg + off; }
+  uint8_t* dev(size_t off) const { return dimg + off; }
+  const uint64_t* dev_table(size_t off) const { return (const uint64_t*)(dimg + off); }
+  const unsigned long long* verdict_words() const { return (const unsigned long long*)(himg + verd); }
+
+  // staged only: bytes [from, to) of the image to the device or back, as one
+  // blocking, counted copy -- page-locked image, idle stream (kPageableRule)
+  int move(size_t from, size_t to, hipMemcpyKind kind) {
+    if (small) return AMPH_OK;
+    uint8_t *dst = kind == hipMemcpyHostToDevice ? dimg : himg, *src = kind == hipMemcpyHostToDevice ? himg : dimg;
+    HIP_TRY(hipMemcpy(dst + from, src + from, to - from, kind));
+    copies->fetch_add(1, std::memory_order_relaxed);
+    return AMPH_OK;
+  }
+
+  // the inputs are in place: to the device, the verdict words reset
+  int upload() {
+    if (int st = move(0, in_bytes, hipMemcpyHostToDevice)) return st;
+    if (n_verd) HIP_TRY(hipMemsetAsync(dverd, 0x7F, 8 * n_verd, s));
+    return AMPH_OK;
+  }
+
+  // after the call's one launch (`e`): outputs and verdict words are in host(...)
+  int finish(hipError_t e, const char* kernel) {
+    if (e == hipSuccess && small && n_verd)
+      e = amph::launch_take_array(dverd, (unsigned long long*)(himg + verd), n_verd, s);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s);
+      return hip_fail(e, kernel);
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return move(in_bytes, total, hipMemcpyDeviceToHost);
+  }
+};
 
 }  // namespace capi

@@ -311,6 +311,21 @@ hipError_t launch_acc_b64(const TextSet& tx, int party, size_t words, size_t nch
 hipError_t launch_mask_sums(const SumSet& sums, size_t words, const uint4* secrets, size_t n_secrets, uint4* out16,
                             char* out24, char* out_text, unsigned long long* first_fail, const Fp& f,
                             const LaunchCfg& c);
+// The same two for K objects (include/amphora_client_batch.h): ONE party's
+// five slotted field buffers (the layout of launch_rv_b64_seg: object o's
+// texts at toff[o], its words packed on woff[n_objects + 1]) added into sums
+// packed on woff; bad_session / bad_call (the latter may be null) are arrays
+// of n_objects words, [o] min-combines (5 party + field) * nchars_o + offset.
+// launch_mask_sums_seg: secrets, out16 / out24 packed on woff, one secret per
+// mask word, or (out_text set) object o's framed text at out_text + ooff[o];
+// first_fail an array of n_objects words with object-local indices.  grid:
+// wire_tile_grid(T, n_objects) or any upper bound of it.  Device tables.
+hipError_t launch_acc_b64_seg(const TextSet& tx, int party, const uint64_t* woff, const uint64_t* toff,
+                              size_t n_objects, size_t grid, const SumSet& sums, unsigned long long* bad_session,
+                              unsigned long long* bad_call, const Fp& f, const LaunchCfg& c);
+hipError_t launch_mask_sums_seg(const SumSet& sums, const uint64_t* woff, const uint64_t* ooff, size_t n_objects,
+                                size_t grid, const uint4* secrets, uint4* out16, char* out24, char* out_text,
+                                unsigned long long* first_fail, const Fp& f, const LaunchCfg& c);
 
 // K_RV / K_MASK from the wire for many objects in one launch (wire.hip, "the
 // slotted text layout"; wiretiles.hpp): object o's texts start toff[o]

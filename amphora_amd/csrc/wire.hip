@@ -570,39 +570,85 @@ __global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_json_seg(TextSet tx, 
 // offset) into a workgroup word in LDS; one lane then min-combines the whole
 // call's encoding, (5 party + field) * nchars + offset, into the session's
 // verdict word and into the call's own (bad_call, may be null).
-template <bool BIG, int BS>
-__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_acc_b64(TextSet tx, int party, size_t words, size_t nchars,
-                                            uint32_t pad, SumSet sums, unsigned long long* bad_session,
-                                            unsigned long long* bad_call, Fp f) {
+//
+// SEG (include/amphora_client_batch.h): K objects' texts in the slotted layout
+// above, the sums packed on woff.  The workgroup decodes one tile of ONE
+// object (seg_tile / seg_fields, the lane-by-lane last tile included) and adds
+// into sums[k][woff[o] + word]; bad_session / bad_call are arrays of n_objects
+// words and take (5 party + field) * nchars_o + offset at [o].  The shape of
+// the launch is the kernel's one argument that differs between the forms, so
+// the one-secret form keeps its arguments and its code.
+template <bool SEG>
+struct AccShape {  // one secret: its words, its text's characters and '=' padding
+  size_t words, nchars;
+  uint32_t pad;
+};
+template <>
+struct AccShape<true> {  // the slotted layout's device tables
+  const uint64_t *woff, *toff;
+  size_t n_objects;
+};
+
+template <bool BIG, int BS, bool SEG>
+__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_acc_b64(TextSet tx, int party, AccShape<SEG> sh, SumSet sums,
+                                            unsigned long long* bad_session, unsigned long long* bad_call, Fp f) {
   __shared__ uint32_t lds[WireGroups<1>::bufs < 2 ? 2 : WireGroups<1>::bufs][3 * BS];
   __shared__ uint32_t lutw[kLutBytes / 4];
   __shared__ unsigned long long wg_bad;
   uint8_t* lutp = reinterpret_cast<uint8_t*>(lutw);
-  b64_lut_fill(lutp);
-  if (threadIdx.x == 0) wg_bad = ~0ULL;
-  __syncthreads();
-  W4 acc[5];
-  uint4 raw[5][1];
-  const bool fast = ((size_t)blockIdx.x + 1) * Wire<BS>::chars + 4 <= nchars;
-  if (fast) {
-    wire_load<1, BS>(tx, raw, blockIdx.x);
-    wire_fields<1, BIG, true, BS>(tx, 1, nchars, pad, words, raw, lds, acc, &wg_bad, f, blockIdx.x, lutp);
-  } else {
-    wire_fields<1, BIG, false, BS>(tx, 1, nchars, pad, words, raw, lds, acc, &wg_bad, f, blockIdx.x, lutp);
-  }
-  const size_t word = (size_t)blockIdx.x * Wire<BS>::words + threadIdx.x;
-  if (threadIdx.x < Wire<BS>::words && word < words) {
+  if constexpr (SEG) {
+    SegTile s;
+    const bool real = seg_tile<BS>(sh.woff, sh.toff, sh.n_objects, s);  // its table loads fly during the fill
+    b64_lut_fill(lutp);
+    if (threadIdx.x == 0) wg_bad = ~0ULL;
+    __syncthreads();
+    if (!real) return;  // (the whole workgroup)
+    W4 acc[5];
+    uint4 raw[5][1];
+    seg_fields<1, BIG, BS>(tx, 1, s, raw, lds, acc, &wg_bad, f, lutp);
+    const size_t word = s.tile * Wire<BS>::words + threadIdx.x;
+    if (threadIdx.x < Wire<BS>::words && word < s.words) {  // s.w0 + s.words <= T: seg_tile's clamp
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      uint4* p = sums.s[k] + word;
-      *p = u4(mod_add(w4(*p), acc[k], f));
+      for (int k = 0; k < 5; ++k) {
+        uint4* p = sums.s[k] + s.w0 + word;
+        *p = u4(mod_add(w4(*p), acc[k], f));
+      }
     }
-  }
-  __syncthreads();  // every lane's report is in wg_bad
-  if (threadIdx.x == 0 && wg_bad != ~0ULL) {
-    const unsigned long long v = wg_bad + (unsigned long long)(5 * (size_t)party) * nchars;
-    atomicMin(bad_session, v);
-    if (bad_call) atomicMin(bad_call, v);
+    __syncthreads();  // every lane's report is in wg_bad
+    if (threadIdx.x == 0 && wg_bad != ~0ULL) {
+      const unsigned long long v = wg_bad + (unsigned long long)(5 * (size_t)party) * s.nchars;
+      atomicMin(bad_session + s.o, v);
+      if (bad_call) atomicMin(bad_call + s.o, v);
+    }
+  } else {
+    const size_t words = sh.words, nchars = sh.nchars;
+    const uint32_t pad = sh.pad;
+    b64_lut_fill(lutp);
+    if (threadIdx.x == 0) wg_bad = ~0ULL;
+    __syncthreads();
+    W4 acc[5];
+    uint4 raw[5][1];
+    const bool fast = ((size_t)blockIdx.x + 1) * Wire<BS>::chars + 4 <= nchars;
+    if (fast) {
+      wire_load<1, BS>(tx, raw, blockIdx.x);
+      wire_fields<1, BIG, true, BS>(tx, 1, nchars, pad, words, raw, lds, acc, &wg_bad, f, blockIdx.x, lutp);
+    } else {
+      wire_fields<1, BIG, false, BS>(tx, 1, nchars, pad, words, raw, lds, acc, &wg_bad, f, blockIdx.x, lutp);
+    }
+    const size_t word = (size_t)blockIdx.x * Wire<BS>::words + threadIdx.x;
+    if (threadIdx.x < Wire<BS>::words && word < words) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        uint4* p = sums.s[k] + word;
+        *p = u4(mod_add(w4(*p), acc[k], f));
+      }
+    }
+    __syncthreads();  // every lane's report is in wg_bad
+    if (threadIdx.x == 0 && wg_bad != ~0ULL) {
+      const unsigned long long v = wg_bad + (unsigned long long)(5 * (size_t)party) * nchars;
+      atomicMin(bad_session, v);
+      if (bad_call) atomicMin(bad_call, v);
+    }
   }
 }
 
@@ -625,6 +671,50 @@ __global__ __launch_bounds__(BS) void k_mask_sums(SumSet sums, size_t words, con
   uint4 s = make_uint4(0, 0, 0, 0);
   if (threadIdx.x < WW && word < n_secrets) s = ld(secrets + word);
   mask_tile_out<1, BS, JSON>(blockIdx.x, words, s, n_secrets, acc, out16, out24, ff, lds, f);
+}
+
+// k_mask_sums for K objects (include/amphora_client_batch.h): the sums, the
+// secrets and out16 / out24 packed on woff, one secret per mask word, ff an
+// array of n_objects words with object-local indices.  The workgroup's object
+// and tile come from the word table alone (wire_tile_find; the word range
+// clamped into [0, woff[n_objects]] as seg_tile does), and mask_tile_out runs
+// unchanged with the object's own tile index and word count.  JSON: object
+// o's framed text goes to out24 + ooff[o] (a multiple of 16), the "[]" of an
+// object of no words comes from workgroup g(o) as in k_mask_json_seg.
+template <int BS, bool JSON>
+__global__ __launch_bounds__(BS) void k_mask_sums_seg(SumSet sums, const uint64_t* woff, const uint64_t* ooff,
+                                                      size_t n_objects, const uint4* secrets, uint4* out16,
+                                                      char* out24, unsigned long long* ff, Fp f) {
+  constexpr int WW = Wire<BS>::words;
+  static_assert(WW == kWireTileWords, "wiretiles.hpp's tile is this workgroup's");
+  // (the framed text image of WW records: 37 WW + 4 bytes, as k_mask_json)
+  __shared__ __attribute__((aligned(16))) uint32_t lds[JSON ? 3 : 1][3 * BS];
+  static_assert(3 * 3 * BS * 4 >= kJsonRec * WW + 4, "the text image fits the buffers");
+  const WireTile wt = wire_tile_find(woff, n_objects, blockIdx.x, WW);
+  const uint64_t T = woff[n_objects];
+  const uint64_t a = woff[wt.object], b = woff[wt.object + 1];
+  const uint64_t w0 = a < T ? a : T, w1 = b < w0 ? w0 : (b < T ? b : T);
+  const size_t words = (size_t)(w1 - w0);
+  if (!wire_tile_real(wt.local, words, WW)) {  // (the whole workgroup)
+    if constexpr (JSON) {
+      char* dst = out24 + ooff[wt.object];
+      if (words == 0 && wt.local == 0 && threadIdx.x < 2) dst[threadIdx.x] = threadIdx.x ? ']' : '[';
+    }
+    return;
+  }
+  W4 acc[5];
+  const size_t word = wt.local * WW + threadIdx.x;
+  const bool in = threadIdx.x < WW && word < words;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) acc[k] = w4(in ? sums.s[k][w0 + word] : make_uint4(0, 0, 0, 0));
+  uint4 s = make_uint4(0, 0, 0, 0);
+  if (in) s = ld(secrets + w0 + word);
+  if constexpr (JSON)
+    mask_tile_out<1, BS, true>(wt.local, words, s, words, acc, nullptr, out24 + ooff[wt.object], ff + wt.object, lds,
+                               f);
+  else
+    mask_tile_out<1, BS>(wt.local, words, s, words, acc, out16 ? out16 + w0 : nullptr,
+                         out24 ? out24 + 24 * w0 : nullptr, ff + wt.object, lds, f);
 }
 
 }  // namespace
@@ -715,10 +805,42 @@ hipError_t launch_acc_b64(const TextSet& tx, int party, size_t words, size_t nch
   if (words == 0) return hipSuccess;
   constexpr int BS = kWireBlock;
   const dim3 g((unsigned)((words + Wire<BS>::words - 1) / Wire<BS>::words));
+  const AccShape<false> sh{words, nchars, pad};
   if (f.big)
-    AMPH_LAUNCH((k_acc_b64<true, BS>), g, dim3(BS), c, tx, party, words, nchars, pad, sums, bad_session, bad_call, f);
+    AMPH_LAUNCH((k_acc_b64<true, BS, false>), g, dim3(BS), c, tx, party, sh, sums, bad_session, bad_call, f);
   else
-    AMPH_LAUNCH((k_acc_b64<false, BS>), g, dim3(BS), c, tx, party, words, nchars, pad, sums, bad_session, bad_call, f);
+    AMPH_LAUNCH((k_acc_b64<false, BS, false>), g, dim3(BS), c, tx, party, sh, sums, bad_session, bad_call, f);
+  return hipGetLastError();
+}
+
+hipError_t launch_acc_b64_seg(const TextSet& tx, int party, const uint64_t* woff, const uint64_t* toff,
+                              size_t n_objects, size_t grid, const SumSet& sums, unsigned long long* bad_session,
+                              unsigned long long* bad_call, const Fp& f, const LaunchCfg& c) {
+  if (grid == 0 || n_objects == 0) return hipSuccess;
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)grid);
+  const AccShape<true> sh{woff, toff, n_objects};
+  if (f.big)
+    AMPH_LAUNCH((k_acc_b64<true, BS, true>), g, dim3(BS), c, tx, party, sh, sums, bad_session, bad_call, f);
+  else
+    AMPH_LAUNCH((k_acc_b64<false, BS, true>), g, dim3(BS), c, tx, party, sh, sums, bad_session, bad_call, f);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_sums_seg(const SumSet& sums, const uint64_t* woff, const uint64_t* ooff, size_t n_objects,
+                                size_t grid, const uint4* secrets, uint4* out16, char* out24, char* out_text,
+                                unsigned long long* ff, const Fp& f, const LaunchCfg& c) {
+  if (grid == 0 || n_objects == 0) return hipSuccess;
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)grid);
+  if (out_text)
+    AMPH_LAUNCH((k_mask_sums_seg<BS, true>), g, dim3(BS), c, sums, woff, ooff, n_objects, secrets, nullptr, out_text,
+                ff, f);
+  else
+    AMPH_LAUNCH((k_mask_sums_seg<BS, false>), g, dim3(BS), c, sums, woff, ooff, n_objects, secrets, out16, out24, ff,
+                f);
   return hipGetLastError();
 }
 

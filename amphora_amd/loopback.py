@@ -31,7 +31,8 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Dict, List, Sequence
 
 from . import _lib
-from .client import (ResponseSession, SecretShareUtil, create_masked_input, create_masked_input_body,
+from .client import (ResponseSession, ResponseSessions, SecretShareUtil, create_masked_input,
+                     create_masked_input_body,
                      create_masked_input_json, verify_output_delivery_objects, verify_vss_json)
 from .entities import (AmphoraClientException, AmphoraServiceException, FactorPair,
                        IllegalArgumentException, MaskedInput, MultiplicationExchangeObject,
@@ -265,6 +266,57 @@ class LoopbackAmphoraClient:
         odos = self._unwrap(self._fan_out(lambda p: p.get_secret_share(secret_id, request_id)))
         data = verify_output_delivery_objects(self.util, odos)
         return Secret(secret_id, list(self.parties[0].secrets[secret_id].tags), data)
+
+    # -- K secrets per round trip (client.ResponseSessions) -----------------------
+    def _fan_in_many(self, fetch) -> ResponseSessions:
+        """_fan_in for K secrets: fetch(party) -> its K bodies, added to one
+        ResponseSessions as they arrive (one launch per party, whatever K is)."""
+        rs = ResponseSessions(self.util, len(self.parties))
+        index = {id(p): i for i, p in enumerate(self.parties)}
+        try:
+            self._unwrap(self._fan_out(lambda p: rs.add_bodies(index[id(p)], fetch(p))))
+        except Exception:
+            rs.close()
+            raise
+        return rs
+
+    @staticmethod
+    def _first_error(outcomes):
+        for x in outcomes:
+            if isinstance(x, Exception):
+                raise x
+        return outcomes
+
+    def get_secrets(self, secret_ids: Sequence[uuid.UUID]) -> List[Secret]:
+        """get_secret for K secrets.  transport="session": every party's K
+        responses go into one ResponseSessions; the first failing secret's
+        exception is raised, as the loop of get_secret raises it.  Other
+        transports: the loop itself."""
+        secret_ids = list(secret_ids)
+        if self.transport != "session" or not secret_ids:
+            return [self.get_secret(s) for s in secret_ids]
+        from . import wire
+        request_ids = [uuid.uuid4() for _ in secret_ids]  # one Output Delivery (and its exchange) per secret
+        with self._fan_in_many(lambda p: [wire.vss_to_json(
+                p.ctx, s, p.secrets[s].tags, p.get_secret_share(s, rid), pretty=False)
+                for s, rid in zip(secret_ids, request_ids)]) as rs:
+            got = self._first_error(rs.secrets(secret_ids))
+        return [Secret(sid, tags, data) for sid, tags, data in got]
+
+    def create_secrets(self, secrets: Sequence[Secret]) -> List[uuid.UUID]:
+        """create_secret for K secrets; transport="session": one
+        ResponseSessions for the K Input Mask responses of every party, then
+        the K uploads."""
+        secrets = list(secrets)
+        if self.transport != "session" or not secrets:
+            return [self.create_secret(s) for s in secrets]
+        from . import wire
+        with self._fan_in_many(lambda p: [wire.odo_to_json(p.ctx, p.get_input_masks(s.secret_id, s.size()))
+                                          for s in secrets]) as rs:
+            texts = self._first_error(rs.masked_input_bodies(secrets))
+        for text in texts:
+            self._check_success(self._fan_out(lambda p, text=text: p.upload_masked_input_body(text)))
+        return [s.secret_id for s in secrets]
 
     def close(self):
         self._pool.shutdown()
