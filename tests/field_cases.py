@@ -474,9 +474,21 @@ BIG_KERNELS = {
     "k_rv_b64_seg": "test_wire_packed",
     "k_mask_b64_seg": "test_wire_packed",
     "k_mask_json_seg": "test_wire_packed",
-    "k_acc_b64": "test_client_session",
+    # `bool SEG` besides `bool BIG`: one test per form, (SEG = false: one secret, SEG = true: K secrets)
+    "k_acc_b64": ("test_client_session", "test_clients_session"),
 }
 BIG_KERNELS_LEFT_OUT = {}  # {kernel: why no test of test_hip_primes.py launches both of its forms}
+
+# Kernels that take the field parameters (an `Fp` argument) and have no BIG form: one code path
+# for every prime, so the guard that keys on `bool BIG` cannot see them.  {kernel: the test of
+# tests/test_hip_primes.py whose calls reach its launcher on all eight primes}.
+FP_KERNELS = {
+    "k_mask_sums": "test_client_session",       # amph_client_finish_mask / _mask_json -> launch_mask_sums
+    "k_mask_sums_seg": "test_clients_session",  # amph_clients_finish_mask / _mask_json -> launch_mask_sums_seg
+    "k_from_gfp": "test_codecs",                # amph_from_gfp -> launch_from_gfp
+    "k_odo_pre": "test_odo_pre",                # amph_odo_pre -> launch_odo_pre
+}
+FP_KERNELS_LEFT_OUT = {}  # {kernel: why no test of test_hip_primes.py launches it}
 
 
 PostRows = namedtuple("PostRows", "W triples own partners")

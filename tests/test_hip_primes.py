@@ -11,8 +11,10 @@ K_ODO_POST, the fused open + post, the wire-fused and segmented kernels, the
 party session, the synthetic inputs; the batch and session kernels:
 k_rv_b64_seg / k_mask_b64_seg / k_mask_json_seg, k_conv_json_seg,
 k_open_post_seg behind the parties session's exchange decode, and the client
-session's k_acc_b64 with k_mask_sums and K_RV over its running sums --
-tests/field_cases.py BIG_KERNELS names the test for each), pins the device lowering of
+session's k_acc_b64 with k_mask_sums and K_RV over its running sums, and the
+K-secret session's segmented k_acc_b64 with k_mask_sums_seg and k_rv_seg over
+sums packed on the word table -- tests/field_cases.py BIG_KERNELS and
+FP_KERNELS name the test for each), pins the device lowering of
 addc / subc / macc96 (mont_mul_ps runs in the wire kernels and for K_MASK's
 secret product, mont_mul_cios in K_RV: both are compared with the same
 reference), and sends partner diffs with raw magnitudes (>= p, negative zero,
@@ -582,6 +584,15 @@ def test_client_session(env, n):
 
 
 # ---- many objects straight from their base64 texts (k_rv_b64_seg, k_mask_b64_seg, k_mask_json_seg) --------
+def per_object(v):
+    """A verdict array of either mode as a list of -1 / value."""
+    if not isinstance(v, np.ndarray):
+        import torch
+        torch.cuda.synchronize()
+        v = host(v)
+    return [-1 if int(x) == NF else int(x) for x in v]
+
+
 def slotted(texts_by_object, sizes, slot_chars):
     """(text offsets, per party the five field buffers): object o's own text at
     the sum of its predecessors' slots, '!' everywhere else."""
@@ -650,6 +661,134 @@ def test_wire_packed(env, n):
             for o in range(K):
                 got = text[int(oo[o]):int(oo[o]) + len(want_texts[o])].tobytes()
                 assert got == want_texts[o], (mode, o)
+
+
+# ---- the client session for K secrets (k_acc_b64's SEG form, k_mask_sums_seg, k_rv_seg over the sums) --------
+CLIENTS_SIZES = [0, 1, 192, 193, 2, 385, 0, 3, 191]  # and one object of the remaining rows (554 of 1,521)
+
+
+def clients_cut(W, witnesses):
+    """The rows as ten objects: CLIENTS_SIZES and the rest.  The list is rotated
+    until the witness words (a sum of exactly p, a carry out of bit 127) do not
+    all lie where an object's own index equals the packed one (object 0, and
+    whatever follows it at word offset 0)."""
+    sizes = CLIENTS_SIZES + [W - sum(CLIENTS_SIZES)]
+    assert sizes[-1] > 0  # (189 words on the prime 3, whose edge set is the smallest; 554 to 1,149 elsewhere)
+    for _ in sizes:
+        woff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+        first = next(int(b) for b in woff[1:] if b)  # the end of the first object that has words
+        if not witnesses or any(i >= first for i in witnesses):
+            return sizes, woff
+        sizes = sizes[1:] + sizes[:1]
+    raise AssertionError("no rotation of the sizes separates the witness words from object 0")
+
+
+@pytest.mark.parametrize("n", FC.PARTY_COUNTS)
+def test_clients_session(env, n):
+    """test_client_session's rows as the ten objects of ONE K-secret session:
+    empty objects first and inside, objects of one word, of exactly one tile, of
+    one word more and of several tiles, so the per-object tiles have uneven
+    prefix sums.  Host mode in all three arrival orders, device mode in the
+    fixed permutation, all three finishes; secrets, masked words, records and
+    the framed texts whole against Python ints and the C oracle; the sums read
+    back at the first and last word and at the coverage words; one fault per
+    position of FC.fault_positions: the owning object's verdict is the local
+    index, every other object is clean."""
+    pr = env.pr
+    rows, odos, oy = env.rv(n)
+    W = rows.W
+    orders = FC.session_orders(n)
+    covs = [FC.assert_session_coverage(pr, rows, order) for order in orders]
+    witnesses = {c[name] for c in covs for name in ("exact_p_at", "carry_at") if c[name] is not None}
+    assert bool(witnesses) == (n >= 2)
+    sizes, woff = clients_cut(W, witnesses)
+    K = len(sizes)
+    cuts = [(int(a), int(b)) for a, b in zip(woff, woff[1:])]
+    assert sizes.count(0) == 2 and cuts[-1][1] == W
+
+    def owner(i):
+        """(object, local index) of packed word i."""
+        o = next(o for o, (lo, hi) in enumerate(cuts) if lo <= i < hi)
+        return o, i - cuts[o][0]
+
+    # the witnesses do not both lie in object 0, nor anywhere else where local and packed indices agree
+    assert not witnesses or any(owner(i)[0] != 0 and cuts[owner(i)[0]][0] > 0 for i in witnesses)
+    cols = (rows.ys, rows.rs, rows.vs, rows.ws, rows.us)
+    sums = FC.running_sums(pr, rows, orders[0])
+    secrets = env.secrets(W)
+    sec = FC.arr(secrets)
+    om, off = env.F.mask_input(sec, odos)
+    assert off == -1 and FC.ints(om) == FC.mask_words(pr, secrets, rows.ys)
+    records = np.frombuffer(b"".join(base64.b64encode(w.tobytes()) for w in om), np.uint8).reshape(W, 24)
+    # the dense layouts, from the word counts alone
+    chars = lambda w: 4 * ((16 * w + 2) // 3)  # noqa: E731
+    toff, bufs = slotted([[[base64.b64encode(f[lo:hi].tobytes()) for f in o] for o in odos] for lo, hi in cuts], sizes,
+                         lambda w: (chars(w) + 15) & ~15)
+    framed = [data_text(om[lo:hi]) for lo, hi in cuts]
+    uoff = np.concatenate([[0], np.cumsum([(len(t) + 15) & ~15 for t in framed])]).astype(np.uint64)
+    assert [len(t) for t in framed] == [37 * w + 1 if w else 2 for w in sizes] and framed[0] == b"[]"
+    want_text = np.full(int(uoff[-1]), 0xA5, np.uint8)
+    for o, t in enumerate(framed):
+        want_text[int(uoff[o]):int(uoff[o]) + len(t)] = np.frombuffer(t, np.uint8)
+    clean = [-1] * K
+    dsec = dev(sec)
+    by_mode = {"host": bufs, "device": [[dev(f) for f in five] for five in bufs]}
+    h = lambda x: x if isinstance(x, np.ndarray) else host(x)  # noqa: E731
+
+    def fed(mode, tx, order):
+        s = env.ctx.clients_begin(woff, n) if mode == "host" else env.ctx.clients_begin_dev(woff, n)
+        assert s.field_offsets.tolist() == toff.tolist() and s.upload_offsets.tolist() == uoff[:-1].tolist()
+        assert (s.field_chars, s.upload_chars) == (bufs[0][0].size, want_text.size)
+        assert [per_object(s.party(j, tx[j])) for j in order] == [clean] * n
+        return s
+
+    def finished(mode, tx, order, finish):
+        """-> (first_fails, bad_chars, the outputs as host arrays, the words read back)."""
+        with fed(mode, tx, order) as s:
+            if finish == "verify":
+                y, ff, bad = s.finish_verify()
+                outs = [y]
+            elif finish == "mask":
+                m16, rec, ff, bad = s.finish_mask(dsec if mode == "device" else sec, records=True, raw=True)
+                outs = [m16, rec]
+            else:
+                out = np.full(want_text.size, 0xA5, np.uint8)
+                text, ff, bad = s.finish_mask_json(dsec if mode == "device" else sec,
+                                                   out=dev(out) if mode == "device" else out)
+                outs = [text]
+            ff, bad = per_object(ff), per_object(bad)
+            return ff, bad, [h(x) for x in outs], {i: s.word(*owner(i)) for i in (picks if finish == "verify" else ())}
+
+    want = {"verify": [oy], "mask": [om, records], "mask_json": [want_text]}
+    for order, cov in zip(orders, covs):
+        picks = {0, W - 1} | {cov[name] for name in ("exact_p_at", "carry_at") if cov[name] is not None}
+        # host mode in every order; device mode launches the same kernels and takes the fixed permutation alone
+        for mode in ("host", "device") if order == orders[-1] else ("host",):
+            for finish in ("verify", "mask", "mask_json"):
+                ff, bad, outs, words = finished(mode, by_mode[mode], order, finish)
+                tag = (mode, order, finish)
+                assert ff == clean and bad == clean, (tag, ff, bad)
+                assert all(g.shape == w.shape and np.array_equal(g, w) for g, w in zip(outs, want[finish])), tag
+                for i, got in words.items():  # the sums, at (object, local index)
+                    assert got == tuple(col[i] for col in cols) == tuple(FC.from_gfp(pr, sums[k][i]) for k in range(5)), \
+                        (tag, i, owner(i))
+    picks = ()
+    for q, at in enumerate(FC.fault_positions(W)):
+        order = orders[q % len(orders)]
+        o, local = owner(at)
+        lo, hi = cuts[o]
+        t = np.frombuffer(base64.b64encode(FC.with_fault(odos, at)[0][3][lo:hi].tobytes()), np.uint8)
+        w_text = bufs[0][3].copy()  # party 0's w: the owning object's text alone changes
+        assert t.size == chars(hi - lo) and not np.array_equal(w_text[int(toff[o]):int(toff[o]) + t.size], t)
+        w_text[int(toff[o]):int(toff[o]) + t.size] = t
+        faulty = clean[:o] + [local] + clean[o + 1:]
+        for mode in ("host", "device"):
+            five = list(by_mode[mode][0])
+            five[3] = w_text if mode == "host" else dev(w_text)
+            tx = [five] + list(by_mode[mode][1:])
+            for finish in ("verify", "mask", "mask_json"):
+                ff, bad, _, _ = finished(mode, tx, order, finish)
+                assert ff == faulty and bad == clean, (mode, at, finish, ff, bad)
 
 
 # ---- many uploads in one launch (k_conv_json_seg) ------------------------------------------------------

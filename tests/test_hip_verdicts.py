@@ -25,6 +25,14 @@ Single-object calls run 1,217 words (a 1,024-lane workgroup edge, six 192-word
 wire tiles and a 65-word tail, base64 padding present); the packed and batch
 calls hold the whole catalogue in one launch, one 257-word object per case, so
 objects are not aligned with waves.
+
+The K-secret client session (amph_clients_*) takes the catalogue as the objects
+of ONE session (tests/verdict_cases.py session_objects): the 257-word objects
+with an honest filler of 0 to 385 words after each, so that the per-object
+192-word tiles of its accumulate and mask kernels have uneven prefix sums, empty
+objects stand next to failing ones and no failing object starts at word 0.  Its
+first_fails are object-local; it writes every object's outputs in both modes,
+and they are compared whole.
 """
 import base64
 import ctypes as C
@@ -51,7 +59,8 @@ BATCH_WORDS = 256  # the host pipeline's batch in these tests
 DEFAULT_BATCH_WORDS = 4 << 20  # capi_internal.hpp
 SINGLE_CALLS = ["recombine_verify", "mask_input", "verify", "recombine_verify_b64", "mask_input_b64", "mask_input_json",
                 "client_verify", "client_mask", "client_mask_json"]
-MANY_CALLS = ["packed", "batch", "wire_packed", "wire_batch", "upload_packed", "upload_batch"]
+MANY_CALLS = ["packed", "batch", "wire_packed", "wire_batch", "upload_packed", "upload_batch",
+              "clients_verify", "clients_mask", "clients_mask_json"]
 OK, E_VERIFY = 0, 1
 
 
@@ -91,6 +100,7 @@ def _release():
     _CTX.clear()
     rows.cache_clear()
     many.cache_clear()
+    clients.cache_clear()
     gc.collect()
 
 
@@ -632,6 +642,129 @@ def run_upload_batch(pid, n):
     assert texts == upload_texts(M)
 
 
+# ---- the K-secret client session: the catalogue as the objects of ONE session -------------------------
+PREFILL = 0xA5
+CLIENTS_MESSAGE = "Verification of secret has failed: object %d at word %d (%d of %d objects failed)"
+
+
+class Clients:
+    """VC.session_objects(pid, n) in the arrays a session takes and gives: per
+    party the five slotted buffers in the dense layout ('!' in every gap and in
+    the tail), the packed secrets, and every expected output whole -- all from
+    the builder's Python-int references."""
+
+    def __init__(self, pid, n):
+        S = self.S = VC.session_objects(pid, n)
+        self.K, self.T = len(S.sizes), S.woff[-1]
+        self.woff = np.asarray(S.woff, np.uint64)
+        self.foff = np.asarray(S.foff, np.uint64)
+        self.bufs = [[np.full(S.field_chars, ord("!"), np.uint8) for _ in range(5)] for _ in range(n)]
+        for o, obj in enumerate(S.objects):
+            at, nc = S.foff[o], VC.wire_text_chars(S.sizes[o])
+            for j, five in enumerate(VC.object_texts(obj)):
+                for k, t in enumerate(five):
+                    assert len(t) == nc
+                    self.bufs[j][k][at:at + nc] = np.frombuffer(t, np.uint8)
+        def packed(words_of):
+            made = {}  # (most objects share their base's words: each distinct tuple becomes an array once)
+            for t in map(words_of, S.objects):
+                if t not in made:
+                    made[t] = FC.arr(t)
+            return np.concatenate([made[words_of(obj)] for obj in S.objects])
+
+        self.sec = packed(lambda obj: obj.secrets)
+        self.y = packed(lambda obj: obj.y)
+        self.m = packed(lambda obj: obj.masked)
+        assert self.sec.shape == self.y.shape == self.m.shape == (self.T, 16)
+        self.rec = np.frombuffer(b"".join(obj.records for obj in S.objects), np.uint8).reshape(self.T, 24)
+        # the framed texts in the dense upload layout; what lies between them stays as pre-filled
+        self.text = np.full(S.upload_chars, PREFILL, np.uint8)
+        for o, obj in enumerate(S.objects):
+            assert len(obj.text) == VC.upload_text_chars(S.sizes[o]) and (S.sizes[o] > 0 or obj.text == b"[]")
+            self.text[S.uoff[o]:S.uoff[o] + len(obj.text)] = np.frombuffer(obj.text, np.uint8)
+        failing = [o for o in range(self.K) if S.ff[o] >= 0]
+        self.status = (E_VERIFY, CLIENTS_MESSAGE % (failing[0], S.ff[failing[0]], len(failing), self.K))
+        # the words read back: every rejected object's failing word, every edited word of classes C and D
+        self.reads = []
+        for o, obj in enumerate(S.objects):
+            at = ({obj.ff} if obj.ff >= 0 else set()) | \
+                ({e[2] for e in obj.case.edits} if obj.kind == "case" and obj.case.cls in "CD" else set())
+            self.reads += [(o, i, tuple(obj.cols[k][i] for k in range(5))) for i in sorted(at)]
+        assert {S.objects[o].case.cls for o, _, _ in self.reads} == set("ACDE") and len(self.reads) > len(failing)
+        self._dev = None
+
+    def device(self):
+        """(the parties' buffers, the secrets) on the device, uploaded once."""
+        if self._dev is None:
+            self._dev = ([[up(f) for f in five] for five in self.bufs], up(self.sec))
+        return self._dev
+
+
+@functools.lru_cache(maxsize=2)  # (the three finishes of one prime and party count run in a row)
+def clients(pid, n):
+    return Clients(pid, n)
+
+
+def run_clients(pid, n, finish):
+    """amph_clients_finish_verify / _mask / _mask_json (`finish`) and their _dev
+    forms on the objects of VC.session_objects: host mode in every order of
+    FC.session_orders(n), device mode in the last one (at most four sessions).
+    Per object: the verdict is the builder's, no illegal character is reported
+    by any call, and the outputs are the builder's WHOLE -- the K session writes
+    every object's outputs whatever its verdict, in both modes, "[]" for an
+    empty object, nothing between the framed texts.  Host status and message
+    follow from the reference verdict list; amph_clients_word gives the five
+    recombined values of the edited rows.  Last, and weaker: the verdict arrays
+    are those of the packed wire-text call on the same buffers."""
+    M = clients(pid, n)
+    S = M.S
+    ctx = _ctx(pid)
+    clean = [-1] * M.K
+    orders = FC.session_orders(n)
+    runs = [(False, order) for order in orders] + [(True, orders[-1])]
+    assert len(runs) <= 4 and sum(f >= 0 for f in S.ff) >= 20
+    host_verdicts = None
+    for on_dev, order in runs:
+        tag = ("device" if on_dev else "host", order)
+        bufs, sec = M.device() if on_dev else (M.bufs, M.sec)
+        with (ctx.clients_begin_dev(M.woff, n) if on_dev else ctx.clients_begin(M.woff, n)) as s:
+            # the dense layout, computed in Python from the word counts alone
+            assert (s.field_chars, s.upload_chars) == (S.field_chars, S.upload_chars), tag
+            assert s.field_offsets.tolist() == list(S.foff) and s.upload_offsets.tolist() == list(S.uoff), tag
+            parts = [s.party(j, bufs[j]) if on_dev else s.party(j, bufs[j], status=True) for j in order]
+            if finish == "verify":
+                res, want = s.finish_verify(status=True), [M.y]
+            elif finish == "mask":
+                res, want = s.finish_mask(sec, records=True, raw=True, status=True), [M.m, M.rec]
+            else:
+                out = np.full(S.upload_chars, PREFILL, np.uint8)
+                res, want = s.finish_mask_json(sec, out=up(out) if on_dev else out, status=True), [M.text]
+            *outs, ff, bad, status = res
+            if on_dev:
+                assert status[0] == OK and all(verdicts(v) == clean for v in parts), tag
+                outs = [down(x) for x in outs]
+            else:
+                assert all(v.tolist() == clean and st == (OK, "") for v, st in parts), tag
+                assert status == M.status, (tag, status)
+                host_verdicts = (ff, bad)
+            assert verdicts(ff) == list(S.ff), (tag, verdicts(ff))
+            assert verdicts(bad) == clean, tag
+            for g, w in zip(outs, want):  # whole: rejected objects, empty objects and the gaps included
+                if not (g.shape == w.shape and np.array_equal(g, w)):
+                    where = np.flatnonzero((g != w).reshape(len(w), -1).any(axis=1))
+                    raise AssertionError((tag, "first difference at row %d of %d" % (where[0], len(w))))
+            for o, i, cols in M.reads:
+                assert s.word(o, i) == cols, (tag, S.objects[o].name, i)
+    # bit for bit what the packed wire-text call says on all parties' buffers at once
+    if finish == "verify":
+        _, ff, bad = ctx.recombine_verify_b64_packed(M.bufs, M.woff, M.foff)
+    elif finish == "mask":
+        _, _, ff, bad = ctx.mask_input_b64_packed(M.bufs, M.woff, M.foff, M.sec, records=True, raw=True)
+    else:
+        _, _, ff, bad = ctx.mask_input_json_packed(M.bufs, M.woff, M.foff, M.sec)
+    assert np.array_equal(host_verdicts[0], ff) and np.array_equal(host_verdicts[1], bad)
+
+
 RUN = {"recombine_verify": run_recombine_verify, "mask_input": run_mask_input, "verify": run_verify,
        "recombine_verify_b64": run_recombine_verify_b64, "mask_input_b64": run_mask_input_b64,
        "mask_input_json": run_mask_input_json, "packed": run_packed, "batch": run_batch,
@@ -639,7 +772,10 @@ RUN = {"recombine_verify": run_recombine_verify, "mask_input": run_mask_input, "
        "client_verify": functools.partial(run_client, finish="verify"),
        "client_mask": functools.partial(run_client, finish="mask"),
        "client_mask_json": functools.partial(run_client, finish="mask_json"),
-       "upload_packed": run_upload_packed, "upload_batch": run_upload_batch}
+       "upload_packed": run_upload_packed, "upload_batch": run_upload_batch,
+       "clients_verify": functools.partial(run_clients, finish="verify"),
+       "clients_mask": functools.partial(run_clients, finish="mask"),
+       "clients_mask_json": functools.partial(run_clients, finish="mask_json")}
 assert list(RUN) and set(RUN) == set(VC.MATRIX.values()) == set(SINGLE_CALLS + MANY_CALLS)
 
 

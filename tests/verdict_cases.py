@@ -52,6 +52,9 @@ MATRIX = {
     "amph_client_finish_verify": "client_verify",
     "amph_client_finish_mask": "client_mask",
     "amph_client_finish_mask_json": "client_mask_json",
+    "amph_clients_finish_verify": "clients_verify",
+    "amph_clients_finish_mask": "clients_mask",
+    "amph_clients_finish_mask_json": "clients_mask_json",
     "amph_recombine_verify_packed": "packed",
     "amph_mask_input_packed": "packed",
     "amph_recombine_verify_batch": "batch",
@@ -335,4 +338,163 @@ def patched(values, changed: dict) -> list:
     out = list(values)
     for i, x in changed.items():
         out[i] = x
+    return out
+
+
+# ---- the catalogue as objects of ONE client session (include/amphora_client_batch.h) -----------
+# The K-secret session accumulates with one workgroup per 192-word tile of ONE object (k_acc_b64's
+# segmented form, k_mask_sums_seg) and verifies with the word-packed k_rv_seg, where an object's
+# border may lie inside a wave.  The layout below makes the tile prefix sums uneven, puts empty
+# objects directly before and after failing ones and no failing object at word 0.
+TILE = 192          # wiretiles.hpp kWireTileWords
+WAVE = 64
+W_SESSION = 257     # one object per catalogue case: two tiles, the second of 65 words
+FILLER_SIZES = (0, 1, 192, 0, 193, 2, 385, 3, 191)
+
+SessionObject = namedtuple("SessionObject", "name kind base case ff cols y secrets masked records text")
+Session = namedtuple("Session", "pid n objects sizes woff foff uoff field_chars upload_chars ff")
+
+
+def wire_text_chars(W: int) -> int:
+    return 4 * ((16 * W + 2) // 3)
+
+
+def wire_slot_chars(W: int) -> int:
+    return (wire_text_chars(W) + 15) & ~15
+
+
+def upload_text_chars(W: int) -> int:
+    return 37 * W + 1 if W else 2
+
+
+def upload_slot_chars(W: int) -> int:
+    return (upload_text_chars(W) + 15) & ~15
+
+
+def record(word: int) -> bytes:
+    """Python's base64 of one 16-byte little-endian word: a 24-character record."""
+    return base64.b64encode(int(word).to_bytes(16, "little"))
+
+
+def data_text(words) -> bytes:
+    """Jackson's compact MaskedInput "data" array of the given words ("[]" for none)."""
+    return b"[" + b",".join(b'{"value":"' + record(w) + b'"}' for w in words) + b"]"
+
+
+def tile_of(woff, o: int, i: int) -> int:
+    """The workgroup that owns word i of object o: g(o) + i / 192 with g(o) = woff[o] / 192 + o."""
+    return woff[o] // TILE + o + i // TILE
+
+
+@functools.lru_cache(maxsize=None)
+def _mask_refs(pid: str, n: int, W: int, y: tuple):
+    """(secrets, masked words, records, framed text) of base(pid, n, W)'s secrets under the masks `y`."""
+    secrets = tuple(secrets_for(base(pid, n, W)))
+    masked = tuple(FC.mask_words(FC.BY_ID[pid], secrets, y))
+    return secrets, masked, b"".join(record(m) for m in masked), data_text(masked)
+
+
+def _session_object(b: Base, name: str, kind: str, case, e: Expect) -> SessionObject:
+    """One object with every expected result, from Python ints alone (objects
+    that recombine to the same secrets share one computation of the mask step)."""
+    cols = tuple(tuple(c) for c in columns(b, case)) if case is not None and case.edits else b.cols
+    y = tuple(patched(b.cols[Y], e.changed))
+    assert y == tuple(cols[Y]), name  # two ways to the same secrets: `expect` and `columns`
+    return SessionObject(name, kind, b, case, e.ff, cols, y, *_mask_refs(b.pid, b.n, b.W, y))
+
+
+@functools.lru_cache(maxsize=None)
+def session_objects(pid: str, n: int) -> Session:
+    """The catalogue as the objects of one K-secret client session: an honest
+    257-word object, one 257-word object per case of catalogue(pid, n, 257),
+    then the pair (`u` off in the last word of one object, `w` off in word 0 of
+    the next: the two objects stay neighbours).  After each of these -- the
+    pair counting as one -- comes ONE honest filler whose size walks
+    FILLER_SIZES, rows from `base` at that size.  Every object carries its
+    expected verdict, secrets, masked words, records and framed text, computed
+    with ``%`` on Python ints; the coverage predicates below are asserted on
+    this layout alone, before any library call."""
+    pr = FC.BY_ID[pid]
+    b, cs = catalogue(pid, n, W_SESSION)
+    W = b.W
+    honest = Expect(-1, {})
+    pair = [single_fault(b, U, W - 1, party=n - 1, name="pair_last_u"), single_fault(b, Wf, 0, party=0, name="pair_first_w")]
+    units = [[_session_object(b, "honest", "honest", None, honest)]]
+    units += [[_session_object(b, c.name, "case", c, e)] for c, e in cs]
+    units.append([_session_object(b, c.name, "pair", c, expect(b, c)) for c in pair])
+    objects = []
+    for q, unit in enumerate(units):
+        objects += unit
+        fb = base(pid, n, FILLER_SIZES[q % len(FILLER_SIZES)])
+        objects.append(_session_object(fb, "filler%d_%d" % (q, fb.W), "filler", None, honest))
+    sizes = [o.base.W for o in objects]
+    K = len(objects)
+
+    def offsets(per):
+        out = [0]
+        for x in per:
+            out.append(out[-1] + x)
+        return out
+
+    woff = offsets(sizes)
+    foff = offsets([wire_slot_chars(w) for w in sizes])
+    uoff = offsets([upload_slot_chars(w) for w in sizes])
+    ff = [o.ff for o in objects]
+    names = [o.name for o in objects]
+    failing = [o for o in range(K) if ff[o] >= 0]
+    # ---- the coverage predicates, on the inputs alone -------------------------------------
+    assert len(names) == len(set(names)) and {c.cls for c, _ in cs} == set("ABCDE")
+    assert all(o.ff == -1 for o in objects if o.kind in ("honest", "filler"))
+    # no failing object starts at word 0: its local verdict differs from its packed index
+    assert failing and all(woff[o] > 0 for o in failing)
+    # a verdict in an object's second tile, and two faults that straddle the tile edge inside one object
+    assert any(ff[o] >= TILE for o in failing)
+    edge = objects[names.index("E_191u_192w")]
+    assert {e[2] for e in edge.case.edits} == {TILE - 1, TILE} and edge.ff == TILE - 1 and edge.base.W > TILE
+    # the pair: neighbours inside one 64-lane wave of the packed words (k_rv_seg) ...
+    lo, hi = names.index("pair_last_u"), names.index("pair_first_w")
+    g = woff[lo + 1] - 1
+    assert hi == lo + 1 and woff[hi] == g + 1 and g // WAVE == (g + 1) // WAVE and (ff[lo], ff[hi]) == (W - 1, 0)
+    # ... and in different objects' tiles (k_acc_b64, k_mask_sums_seg)
+    assert tile_of(woff, lo, W - 1) != tile_of(woff, hi, 0)
+    # an empty object directly before one failing object and directly after another
+    assert any(sizes[o] == 0 and ff[o + 1] >= 0 for o in range(K - 1))
+    assert any(sizes[o] == 0 and ff[o - 1] >= 0 for o in range(1, K))
+    # a failing object at a packed offset that is no multiple of the tile
+    assert any(woff[o] % TILE for o in failing)
+    # every tile count and prefix the fillers are there for: uneven prefix sums
+    assert len({woff[o] % TILE for o in range(K)}) > len(FILLER_SIZES)
+    # words >= p in each of the five fields, from the first party and from the last
+    for j in (0, n - 1):
+        for k in range(5):
+            assert any(w >= pr.p for w in b.odos[j][k]), (pid, n, j, k)
+    return Session(pid, n, tuple(objects), tuple(sizes), tuple(woff), tuple(foff[:-1]), tuple(uoff[:-1]), foff[-1],
+                   uoff[-1], tuple(ff))
+
+
+def object_rows(obj: SessionObject):
+    """[party][field] -> the object's raw words as ints, its case's edits applied."""
+    rows = [list(o) for o in obj.base.odos]
+    for j, k, i, new in (obj.case.edits if obj.case is not None else ()):
+        if isinstance(rows[j][k], tuple):
+            rows[j][k] = list(rows[j][k])
+        rows[j][k][i] = new
+    return rows
+
+
+@functools.lru_cache(maxsize=None)
+def _base_arrays_and_texts(pid: str, n: int, W: int):
+    arrays = base_arrays(base(pid, n, W))
+    return arrays, tuple(tuple(b64(f) for f in o) for o in arrays)
+
+
+def object_texts(obj: SessionObject):
+    """[party][field] -> Python's base64 of the object's words, edits applied
+    (only the edited fields are encoded again)."""
+    arrays, texts = _base_arrays_and_texts(obj.base.pid, obj.base.n, obj.base.W)
+    out = [list(o) for o in texts]
+    if obj.case is not None and obj.case.edits:
+        edited, hit = apply(arrays, obj.case)
+        for j, k in hit:
+            out[j][k] = b64(edited[j][k])
     return out
