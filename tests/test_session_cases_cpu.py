@@ -40,21 +40,35 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- the verdict matrix covers the headers ---------------------------------------------
-def first_fail_prototypes(text):
+FIRST_FAIL = r"first_fails?"
+
+
+def prototypes_with(text, parameter):
     """The names, in order, of the prototypes in the header `text` that take an
-    `int64_t* first_fail` or an `int64_t* first_fails` (comments do not count)."""
+    `int64_t*` whose name matches the pattern `parameter` (comments do not
+    count).  tests/test_text_cases_cpu.py reads the text verdicts with it."""
     src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return [m.group(1) for m in re.finditer(r"\b(amph_[a-z0-9_]+)\s*\(([^;{()]*)\)\s*;", src)
-            if re.search(r"\bint64_t\s*\*\s*first_fails?\b", m.group(2))]
+            if re.search(r"\bint64_t\s*\*\s*(?:%s)\b" % parameter, m.group(2))]
+
+
+def first_fail_prototypes(text):
+    """... that take an `int64_t* first_fail` or an `int64_t* first_fails`."""
+    return prototypes_with(text, FIRST_FAIL)
+
+
+def declarations_with(parameter):
+    """{function name: header} of every prototype of include/*.h with such a parameter."""
+    out = {}
+    for path in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):
+        for name in prototypes_with(open(path).read(), parameter):
+            out[name] = os.path.basename(path)
+    return out
 
 
 def declarations_with_first_fail():
     """{function name: header} of every prototype with a `first_fail(s)` parameter."""
-    out = {}
-    for path in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):
-        for name in first_fail_prototypes(open(path).read()):
-            out[name] = os.path.basename(path)
-    return out
+    return declarations_with(FIRST_FAIL)
 
 
 def test_the_parser_finds_both_spellings_and_nothing_else():

@@ -244,8 +244,9 @@ _ALPHABET = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/"
 
 
 def test_b64_every_character_in_every_unit_position(ctx, F):
-    """The fused kernels' decode (b64.hpp dec4_values6: 6-bit value path, '/'
-    routed through the roll selector) character by character, on the fast
+    """The fused kernels' decode (b64.hpp dec_unit16_lut: sixteen lookups in
+    the workgroup's LDS table; a unit it flags goes to dec4_values, which
+    names the first offender) character by character, on the fast
     path (the first workgroup's units): every alphabet character at each of
     a unit's 16 positions must decode as Python's base64 says -- K_RV's
     secrets and verdict and K_MASK's masked words equal the oracle on the
