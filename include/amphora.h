@@ -546,7 +546,7 @@ int amph_mask_input_json(amph_ctx* ctx, const amph_odo_b64* mask_odos, int n_par
  *   *bad_index = its byte offset; a count other than npairs pairs returns
  *   AMPH_E_LEN (*bad_index = len).  Magnitudes must be < 2^128.  Device mode:
  *   bad_index is a device word (AMPH_NO_FAILURE when clean, len on a count
- *   mismatch). */
+ *   mismatch).  The grammar and the offset in full: the end of this file. */
 size_t amph_exchange_max_chars(size_t npairs);
 int amph_exchange_encode(amph_ctx* ctx, const uint8_t* mag16, const uint8_t* neg, size_t npairs,
                          char* out, size_t out_cap, uint64_t* out_len, uint32_t flags,
@@ -720,6 +720,34 @@ int amph_stream_probe(amph_ctx* ctx, const amph_odo* odos, int n_parties, const 
  * ragged parties (stream-ordered allocation), the *_dev sessions (host-side
  * session state, events across streams) and every call listed above as
  * waiting for its stream. */
+
+/* ---- Beaver exchange decode: the grammar and the offset rule -----------------
+ * (amph_exchange_decode and every call that reports as it does: the packed and
+ * batch forms, amph_party_partner, amph_parties_partner and their _dev forms.)
+ * The grammar: ws [ ws ( pair ( ws , ws pair )* )? ws ] ws EOF with
+ * pair = { ws key ws : ws NUM ws , ws key ws : ws NUM ws }, the keys the
+ * three-byte tokens "a" and "b", one each; ws the four JSON whitespace bytes
+ * (no other control byte); NUM = -?(0|[1-9][0-9]{0,38}), "-0" read as 0 with
+ * sign byte 0.  A key written with a backslash escape (the six characters
+ * backslash u 0 0 6 1 for the a) is refused, though Jackson would take it;
+ * so is every byte >= 0x80.
+ * The offset: the values are numbered by the colons before them, and a
+ * value's token starts at the first non-whitespace byte after its colon.
+ * *bad_index is the smallest of: the token start of a value that is no NUM;
+ * the token start of a value whose surroundings break the grammar -- its key
+ * and opener on the left ('[' ws '{' for the first value, <digit> ws '}' ws
+ * ',' ws '{' for a later first member, ',' for a second member), its ','
+ * or '}' on the right ('}' ws ']' ws EOF for value 2 * npairs - 1), the tie
+ * of its opener to the previous value's last digit ('{"a":1,"b":2}5},{...'
+ * is reported at the value behind the stray bytes, '{"a":1,7,"b":2}' at
+ * "b"'s), a key equal to its first member's (at the second member), or a
+ * number at or beyond 2 * npairs (so a text with too many pairs is
+ * AMPH_E_PARAM at the value that should have closed the array); the first
+ * non-whitespace byte when it is not '[', the last one when it is not ']';
+ * with npairs == 0, the first non-whitespace byte between the brackets.  A
+ * colon whose token the end of the text cuts off reports len.  A text with
+ * none of these and fewer than npairs pairs gets len (AMPH_E_LEN): bytes
+ * between its last '}' and the ']' are then not looked at. */
 
 #ifdef __cplusplus
 }

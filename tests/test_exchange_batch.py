@@ -17,6 +17,7 @@ import pytest
 
 from oracle import amphora_oracle as O
 from oracle import coracle
+from tests import exchange_cases as EC
 from tests import extent_cases as X
 from tests import field_cases as FC
 from tests.test_exchange_batch_cpu import BROKEN_DEVICE_TABLES
@@ -327,13 +328,16 @@ def fault_cases():
 
 
 def single_verdict(text, npairs):
-    """(status, bad_index) of amph_exchange_decode on one text alone."""
+    """(status, bad_index) of amph_exchange_decode on one text alone; they are
+    those of the header's rule (tests/exchange_cases.first_bad)."""
     L, ctx = _L(), _ctx()
     a = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
     mag, neg = np.zeros((npairs + 1, 32), np.uint8), np.zeros((npairs + 1, 2), np.uint8)
     bad = C.c_int64(-1)
     st = L.lib.amph_exchange_decode(ctx._h, a.ctypes.data, len(text), npairs, mag.ctypes.data, neg.ctypes.data,
                                     C.byref(bad), 0, None)
+    rule = EC.first_bad(text, npairs)
+    assert (st, bad.value) == ({"ok": OK, "param": E_PARAM, "len": E_LEN}[rule.kind], rule.bad), (st, bad.value, rule)
     return st, bad.value
 
 

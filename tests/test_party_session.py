@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import amphora_oracle as O
+from tests import exchange_cases as EC
 
 P, R, RINV = O.TEST_PRIME, O.TEST_R, O.TEST_RINV
 
@@ -356,6 +357,9 @@ def test_session_partner_fuzz_matches_pair_decode(ctx, F):
             ref = None
         except ValueError as e:
             ref = str(e)
+        rule = EC.first_bad(t, 2 * W)  # the single call's verdict is the header's rule's
+        assert ref == {"ok": None, "param": "Malformed FactorPair JSON at offset %d" % rule.bad,
+                       "len": "interimValues must hold exactly %d FactorPairs" % (2 * W)}[rule.kind], (trial, kind, pos)
         s = ctx.party_begin(shares[0], 32, masks[0], triples[0], n, want_yrv=False)
         try:
             s.partner(1, t)

@@ -86,8 +86,8 @@ MATRIX = {
     "amph_clients_finish_mask": Entry("field", "clients", _SESSIONS),
     "amph_clients_finish_mask_json": Entry("field", "clients", _SESSIONS),
 }
-_GRAMMAR = ("reads the Beaver exchange's JSON number grammar, not base64: test_wire.py::test_exchange_decode_mutations "
-            "and the fault tables of test_exchange_batch.py / test_party_batch.py hold it to its own grammar oracle")
+_GRAMMAR = ("reads the Beaver exchange's JSON number grammar, not base64: a key of tests/exchange_cases.MATRIX, whose "
+            "catalogue runs through it in tests/test_hip_exchange_texts.py")
 LEFT_OUT = {name: _GRAMMAR for name in (
     "amph_exchange_decode", "amph_exchange_decode_packed", "amph_exchange_decode_batch",
     "amph_party_partner", "amph_parties_partner")}
