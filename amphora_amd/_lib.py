@@ -223,6 +223,10 @@ def _load():
     L.amph_clients_copies.argtypes = [vp]
     L.amph_clients_free.restype = None
     L.amph_clients_free.argtypes = [vp]
+    # include/amphora_client_bodies.h
+    L.amph_bodies_scan.argtypes = [C.c_char_p, sz, vp, vp]
+    L.amph_bodies_party.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(sz), vp]
+    L.amph_bodies_party_dev.argtypes = [vp, i32, vp, sz, vp, vp]
     return L
 
 
@@ -310,7 +314,27 @@ EXPORTED_CLIENTS_SESSION = ["amph_clients_begin", "amph_clients_begin_dev", "amp
                             "amph_clients_finish_mask", "amph_clients_finish_mask_dev",
                             "amph_clients_finish_mask_json", "amph_clients_finish_mask_json_dev",
                             "amph_clients_word", "amph_clients_copies", "amph_clients_free"]
+# what include/amphora_client_bodies.h declares
+EXPORTED_CLIENT_BODIES = ["amph_bodies_scan", "amph_bodies_party", "amph_bodies_party_dev"]
+AMPH_BODY_ABSENT = (1 << 64) - 1
 ODO_FIELD_NAMES = ("secretShares", "rShares", "vShares", "wShares", "uShares")
+
+
+class BodyNotPlain(ValueError):
+    """amph_bodies_scan refused a body (anything but the plain form): the
+    caller parses it its own way (wire.odo_field_texts)."""
+
+
+def bodies_scan(body: bytes):
+    """amph_bodies_scan: -> (starts[5], lens[5]) (uint64 arrays) of the five
+    top-level base64 members of one response body, in ODO order; raises
+    BodyNotPlain with the scanner's reason for anything but the plain form."""
+    out = np.empty((2, 5), np.uint64)
+    st = lib.amph_bodies_scan(body, len(body), out[0].ctypes.data, out[1].ctypes.data)
+    if st == AMPH_E_PARAM:
+        raise BodyNotPlain(lib.amph_last_error().decode())
+    Context._check(st)
+    return out[0], out[1]
 
 
 def wire_text_chars(words: int) -> int:
@@ -1942,6 +1966,67 @@ class ClientSessions:
                 bufs = [torch.from_numpy(np.ascontiguousarray(b)).to("cuda:%d" % self.ctx.device) for b in bufs]
             return self.party(slot, bufs)
         return self.party(slot, bufs, status=status)
+
+    def scan_bodies(self, bodies):
+        """K bodies (bytes) -> the (K, 5) uint64 starts for party_bodies, by
+        bodies_scan; a member of another length than its object's raises
+        AmphoraNativeError(AMPH_E_LEN), a body that is not plain BodyNotPlain."""
+        _need(len(bodies) == self.objects, "expected %d bodies, got %d" % (self.objects, len(bodies)))
+        starts = np.empty((self.objects, 5), np.uint64)
+        for o, (b, nc) in enumerate(zip(bodies, self.field_lens())):
+            starts[o], lens = bodies_scan(b)
+            if (lens != nc).any():
+                raise AmphoraNativeError(AMPH_E_LEN, "object %d: base64 fields of %s characters, expected %d for %d "
+                                                     "words" % (o, [int(x) for x in lens], nc, self.object_words(o)))
+        return starts
+
+    def party_bodies(self, slot: int, bodies, starts=None, status: bool = False):
+        """amph_bodies_party: party `slot`'s K response bodies (bytes) as they
+        are -- K pointers to the K objects, no join, no gather; starts: the
+        (K, 5) byte starts of the five members inside each body (scan_bodies
+        when None), AMPH_BODY_ABSENT in a row marks the object absent.  One
+        launch whatever K is.  Raises ValueError with the packed calls'
+        message when any object holds an illegal character, unless status
+        (then -> (status, message)); the slot counts as taken either way.  A
+        device-mode session lays the bodies out in one device buffer
+        (party_bodies_dev takes a buffer that is already there)."""
+        if starts is None:
+            starts = self.scan_bodies(bodies)
+        st_ = np.ascontiguousarray(starts, dtype=np.uint64)
+        _need(st_.shape == (self.objects, 5) and len(bodies) == self.objects,
+              "one body and five starts per object (%d objects)" % self.objects)
+        if self.dev:
+            import torch
+            at = np.concatenate([[0], np.cumsum([(len(b) + 15) & ~15 for b in bodies])]).astype(np.uint64)
+            buf = np.zeros(max(int(at[-1]), 16), np.uint8)
+            for b, a in zip(bodies, at):
+                buf[int(a):int(a) + len(b)] = np.frombuffer(bytes(b), np.uint8)
+            with torch.cuda.stream(self.stream):  # the upload is ordered before the launch that reads it
+                dbuf = torch.from_numpy(buf).to("cuda:%d" % self.ctx.device)
+            absent = (st_ == AMPH_BODY_ABSENT).any(axis=1)
+            return self.party_bodies_dev(slot, dbuf, np.where(absent[:, None], st_, st_ + at[:-1, None]))
+        K = self.objects
+        ptrs = (C.c_char_p * K)(*[bytes(b) if not isinstance(b, bytes) else b for b in bodies])
+        lens = (C.c_size_t * K)(*[len(b) for b in bodies])
+        st = lib.amph_bodies_party(self._h, slot, ptrs, lens, _ptr(st_))
+        msg = lib.amph_last_error().decode() if st != AMPH_OK else ""
+        if st == AMPH_E_PARAM and msg.startswith("object ") and "Illegal base64 character" in msg:
+            if status:
+                return st, msg
+            raise ValueError(msg)
+        Context._check(st)
+        return (st, msg) if status else None
+
+    def party_bodies_dev(self, slot: int, buffer, starts):
+        """amph_bodies_party_dev: `buffer` is a uint8 device tensor (16-byte
+        aligned) that holds the K bodies anywhere, starts the (K, 5) absolute
+        byte starts (a host array).  Only enqueues; the buffer must stay alive
+        until the session's stream has run the launch."""
+        st_ = np.ascontiguousarray(starts, dtype=np.uint64)
+        _need(st_.shape == (self.objects, 5), "five starts per object (%d objects)" % self.objects)
+        if not self.dev or not _is_dev(buffer):
+            raise ValueError("a device-mode session and a device tensor")
+        Context._check(lib.amph_bodies_party_dev(self._h, slot, _ptr(buffer), buffer.numel(), _ptr(st_), self._sp()))
 
     def _verdicts(self):
         """(first_fails, bad_chars): host arrays start at -1, so a call that is

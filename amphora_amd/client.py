@@ -586,18 +586,24 @@ class ResponseSession:
 
 class ResponseSessions:
     """ResponseSession for K secrets (include/amphora_client_batch.h): every
-    party hands in its K response bodies at once (add_bodies: their 5 K base64
-    member strings are gathered into five slotted buffers and added into the
-    running sums in ONE launch; any thread may hand in its own party), and
+    party hands in its K response bodies at once (add_bodies: the bodies go to
+    the session as they are -- include/amphora_client_bodies.h: each is scanned
+    in C for its five base64 members and the kernel decodes them where they
+    lie, ONE launch; any thread may hand in its own party), and
     secrets / masked_input_bodies finish from the sums -- one entry per
     secret, the value or that secret's exception, as verify_vss_json_batch /
     create_masked_input_bodies return on the same bodies.  The first party's K
     bodies fix the word table; only party 0's bodies are kept as text (their
-    tags)."""
+    tags).
 
-    def __init__(self, util: SecretShareUtil, n_parties: int):
+    in_place=False, or any body of a call that the scanner refuses (an escape
+    in a member, a duplicate, a null ...) or whose members are not ASCII:
+    that call's 5 K member strings are cut out by wire.odo_field_texts and
+    gathered into five slotted buffers, the path that defines every outcome."""
+
+    def __init__(self, util: SecretShareUtil, n_parties: int, in_place: bool = True):
         import threading
-        self._util, self._n = util, n_parties
+        self._util, self._n, self._in_place = util, n_parties, in_place
         self._lock = threading.Lock()
         self._session = None
         self._words = None   # per object, fixed by the first party that arrives
@@ -608,12 +614,13 @@ class ResponseSessions:
     def words(self):
         return self._words
 
-    def _begin(self, texts):
+    def _begin(self, shapes):
+        """shapes: per object (characters of its secretShares, its last two)."""
         from . import wire
         words, errors = [], []
-        for t in texts:
+        for nchars, last2 in shapes:
             try:
-                words.append(wire.words_of_b64(len(t[0]), t[0][-2:]))
+                words.append(wire.words_of_b64(nchars, last2))
                 errors.append(None)
             except ValueError as e:  # not whole words: this secret alone fails
                 words.append(0)
@@ -627,12 +634,16 @@ class ResponseSessions:
         first party's).  A malformed body or a bad character fails its own
         secret only; the finish reports it."""
         from . import wire
+        scans = self._scan(bodies) if self._in_place else None
+        if scans is not None:
+            return self._add_in_place(party_index, bodies, *scans)
+        bodies = [b if isinstance(b, str) else bytes(b).decode("utf-8") for b in bodies]
         texts = [wire.odo_field_texts(b)[0] for b in bodies]
         if party_index == 0:
             self._bodies0 = list(bodies)
         with self._lock:
             if self._session is None:
-                self._begin(texts)
+                self._begin([(len(t[0]), t[0][-2:]) for t in texts])
             if len(texts) != len(self._words):
                 raise AmphoraClientException("party %d answered %d of %d secrets" % (
                     party_index, len(texts), len(self._words)))
@@ -649,6 +660,43 @@ class ResponseSessions:
                     f = t[k].encode("ascii", errors="replace") if isinstance(t[k], str) else bytes(t[k])
                     bufs[k, at:at + nc] = np.frombuffer(f, np.uint8)
         s.party(party_index, [bufs[k, :s.field_chars] for k in range(5)], status=True)
+
+    @staticmethod
+    def _scan(bodies):
+        """-> (the bodies as bytes, starts (K, 5), lens (K, 5)), or None when
+        any body is not plain or a member holds a non-ASCII byte (the gather
+        path replaces such a character, one for one: its verdict is the
+        reference)."""
+        raw = [b.encode("utf-8") if isinstance(b, str) else bytes(b) for b in bodies]
+        starts, lens = np.empty((len(raw), 5), np.uint64), np.empty((len(raw), 5), np.uint64)
+        try:
+            for o, r in enumerate(raw):
+                starts[o], lens[o] = _lib.bodies_scan(r)
+        except _lib.BodyNotPlain:
+            return None
+        for o, (b, r) in enumerate(zip(bodies, raw)):
+            if not (b.isascii() if isinstance(b, str) else r.isascii()):  # (str.isascii costs nothing)
+                if not all(r[int(a):int(a) + int(n)].isascii() for a, n in zip(starts[o], lens[o])):
+                    return None
+        return raw, starts, lens
+
+    def _add_in_place(self, party_index: int, bodies, raw, starts, lens) -> None:
+        if party_index == 0:
+            self._bodies0 = [b if isinstance(b, str) else r.decode("utf-8") for b, r in zip(bodies, raw)]
+        with self._lock:
+            if self._session is None:
+                self._begin([(int(n[0]), r[int(a[0]) + max(int(n[0]) - 2, 0):int(a[0]) + int(n[0])].decode("ascii"))
+                             for r, a, n in zip(raw, starts, lens)])
+            if len(raw) != len(self._words):
+                raise AmphoraClientException("party %d answered %d of %d secrets" % (
+                    party_index, len(raw), len(self._words)))
+            s = self._session
+            for o, nc in enumerate(s.field_lens()):
+                if self._errors[o] is None and (lens[o] != nc).any():
+                    self._errors[o] = AmphoraClientException("The provided shares must be of the same length")
+                if self._errors[o] is not None:  # absent: what a slot left zero reports, in this object alone
+                    starts[o] = _lib.AMPH_BODY_ABSENT
+        s.party_bodies(party_index, raw, starts, status=True)
 
     def _outcomes(self, ff, bad, value):
         out = []

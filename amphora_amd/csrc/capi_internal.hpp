@@ -8,7 +8,8 @@
 // extension headers include/amphora_wire_batch.h,
 // include/amphora_upload_batch.h, include/amphora_respond_batch.h,
 // include/amphora_exchange_batch.h, include/amphora_party_batch.h,
-// include/amphora_client_session.h and include/amphora_client_batch.h declare.
+// include/amphora_client_session.h, include/amphora_client_batch.h and
+// include/amphora_client_bodies.h declare.
 //
 // Host-pointer calls stream the word arrays through the device in batches
 // (ctx->batch_words, default 4 Mi words): per batch the inputs go HtoD on the
@@ -42,6 +43,7 @@
 #include "../../include/amphora_party_batch.h"
 #include "../../include/amphora_client_session.h"
 #include "../../include/amphora_client_batch.h"
+#include "../../include/amphora_client_bodies.h"
 #include "host_stream.hpp"
 #include "kernels.hpp"
 #include "wiretiles.hpp"
@@ -178,7 +180,36 @@ struct amph_ctx {
   std::atomic<uint64_t> worker_tasks{0};
 };
 
+// The client session for K secrets (include/amphora_client_batch.h,
+// clients_session.hip; the body calls of include/amphora_client_bodies.h,
+// clients_bodies.hip, hand a party in on the same session).
+struct amph_clients {
+  amph_ctx* c = nullptr;
+  size_t K = 0, T = 0;
+  int n = 0;
+  bool dev = false;
+  hipStream_t dstream = nullptr;  // device mode: the stream of the latest call
+  std::vector<uint64_t> woff, foff, uoff;  // word (K + 1), field text (K) and framed text (K) offsets
+  size_t field_chars = 0, used_chars = 0, upload_chars = 0;  // used: the end of the last field text
+  DevBuf mem;
+  amph::PinnedBuf tables_host;  // device mode: the image the tables are uploaded from
+  amph::SumSet sums{};
+  // device tables, contiguous in this order (one upload): word, field text, framed text offsets
+  uint64_t *d_woff = nullptr, *d_foff = nullptr, *d_uoff = nullptr;
+  unsigned long long* d_bad = nullptr;  // K words: min over the parties, the packed calls' encoding
+  // device mode, the body calls: the device starts[5][K] (rewritten in stream order by each call) and the
+  // page-locked images it is uploaded from, one per party slot (in tables_host, behind the tables)
+  uint64_t *d_starts = nullptr, *starts_host = nullptr;
+  std::vector<unsigned long long> bad_host;  // host mode: the same, as the party calls returned it
+  uint32_t have = 0;  // bit j: party j's texts are in the sums
+  bool finished = false;
+  ~amph_clients() { tables_host.release(); }
+};
+
 namespace capi __attribute__((visibility("hidden"))) {
+
+// what every call on a client batch session checks first (clients_session.hip)
+int clients_check(amph_clients* p, bool dev, bool open);
 
 // a context allocation that frees the pooled party-session buffers and tries
 // once more when memory runs out (capi_ctx.hip)

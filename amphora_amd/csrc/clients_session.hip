@@ -17,29 +17,8 @@
 // tables by one hipMemcpyAsync from a page-locked image the session owns.
 #include "capi_internal.hpp"
 
-struct amph_clients {
-  amph_ctx* c = nullptr;
-  size_t K = 0, T = 0;
-  int n = 0;
-  bool dev = false;
-  hipStream_t dstream = nullptr;  // device mode: the stream of the latest call
-  std::vector<uint64_t> woff, foff, uoff;  // word (K + 1), field text (K) and framed text (K) offsets
-  size_t field_chars = 0, used_chars = 0, upload_chars = 0;  // used: the end of the last field text
-  DevBuf mem;
-  amph::PinnedBuf tables_host;  // device mode: the image the tables are uploaded from
-  amph::SumSet sums{};
-  // device tables, contiguous in this order (one upload): word, field text, framed text offsets
-  uint64_t *d_woff = nullptr, *d_foff = nullptr, *d_uoff = nullptr;
-  unsigned long long* d_bad = nullptr;  // K words: min over the parties, the packed calls' encoding
-  std::vector<unsigned long long> bad_host;  // host mode: the same, as the party calls returned it
-  uint32_t have = 0;  // bit j: party j's texts are in the sums
-  bool finished = false;
-  ~amph_clients() { tables_host.release(); }
-};
-
-namespace {
-size_t clients_table_bytes(size_t K) { return 8 * (3 * K + 1); }
-
+// (struct amph_clients: capi_internal.hpp -- clients_bodies.hip works on the same session)
+namespace capi {
 int clients_check(amph_clients* p, bool dev, bool open) {
   if (!p || !p->c) return fail(AMPH_E_PARAM, "null client batch session");
   if (p->dev != dev)
@@ -48,6 +27,10 @@ int clients_check(amph_clients* p, bool dev, bool open) {
   if (open && p->finished) return fail(AMPH_E_PARAM, "the client batch session is already finished");
   return AMPH_OK;
 }
+}  // namespace capi
+
+namespace {
+size_t clients_table_bytes(size_t K) { return 8 * (3 * K + 1); }
 
 int clients_all_in(const amph_clients* p) {
   for (int j = 0; j < p->n; ++j)
@@ -99,7 +82,8 @@ int clients_begin(amph_ctx* c, const uint64_t* woff, size_t K, int n_parties, bo
   if (dev) p->dstream = stream;
   else if (int st = host_stream(c, 0, &p->dstream)) return st;
   const size_t field = align256(16 * p->T), tab = align256(clients_table_bytes(K));
-  if (pool_ensure(c, p->mem, 5 * field + tab + align256(8 * K)) != hipSuccess)
+  // (behind the verdict words: the body calls' starts[5][K], device mode -- include/amphora_client_bodies.h)
+  if (pool_ensure(c, p->mem, 5 * field + tab + align256(8 * K) + (dev ? align256(40 * K) : 0)) != hipSuccess)
     return fail(AMPH_E_NOMEM, "client batch session device memory");
   uint8_t* base = (uint8_t*)p->mem.p;
   for (int k = 0; k < 5; ++k) p->sums.s[k] = (uint4*)(base + k * field);
@@ -107,17 +91,20 @@ int clients_begin(amph_ctx* c, const uint64_t* woff, size_t K, int n_parties, bo
   p->d_foff = p->d_woff + K + 1;
   p->d_uoff = p->d_foff + K;
   p->d_bad = (unsigned long long*)(base + 5 * field + tab);
+  if (dev) p->d_starts = (uint64_t*)(base + 5 * field + tab + align256(8 * K));
   std::vector<uint64_t> img(clients_table_bytes(K) / 8);
   std::copy(p->woff.begin(), p->woff.end(), img.begin());
   std::copy(p->foff.begin(), p->foff.end(), img.begin() + K + 1);
   std::copy(p->uoff.begin(), p->uoff.end(), img.begin() + 2 * K + 1);
   hipError_t e = hipSuccess;
   if (dev) {
-    if (p->tables_host.ensure(clients_table_bytes(K)) != hipSuccess) {
+    // (after the tables: one starts[5][K] image per party slot for the body calls)
+    if (p->tables_host.ensure(clients_table_bytes(K) + (size_t)n_parties * 40 * K) != hipSuccess) {
       pool_put(c, p->mem);
       return fail(AMPH_E_NOMEM, "client batch session page-locked tables");
     }
     std::memcpy(p->tables_host.p, img.data(), clients_table_bytes(K));
+    p->starts_host = (uint64_t*)((uint8_t*)p->tables_host.p + clients_table_bytes(K));
     e = hipMemcpyAsync(p->d_woff, p->tables_host.p, clients_table_bytes(K), hipMemcpyHostToDevice, p->dstream);
   } else {
     // the context's stream is idle between host calls (kPageableRule)

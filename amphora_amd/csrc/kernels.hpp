@@ -326,6 +326,16 @@ hipError_t launch_acc_b64_seg(const TextSet& tx, int party, const uint64_t* woff
 hipError_t launch_mask_sums_seg(const SumSet& sums, const uint64_t* woff, const uint64_t* ooff, size_t n_objects,
                                 size_t grid, const uint4* secrets, uint4* out16, char* out24, char* out_text,
                                 unsigned long long* first_fail, const Fp& f, const LaunchCfg& c);
+// launch_acc_b64_seg on the texts where a party's response bodies hold them
+// (include/amphora_client_bodies.h; bodyspans.hpp): `buffer` is 16-byte
+// aligned device memory whose allocation reaches the next multiple of 16 past
+// the last text, starts[5][n_objects] (a device table) gives the byte where
+// object o's field k begins -- any residue mod 16 -- or ~0 in field 0 for an
+// object that is absent: it reports (5 party) * nchars_o and adds nothing.
+// Only aligned 16-byte granules that hold text are read.
+hipError_t launch_acc_b64_bodies(const char* buffer, int party, const uint64_t* woff, const uint64_t* starts,
+                                 size_t n_objects, size_t grid, const SumSet& sums, unsigned long long* bad_session,
+                                 unsigned long long* bad_call, const Fp& f, const LaunchCfg& c);
 
 // K_RV / K_MASK from the wire for many objects in one launch (wire.hip, "the
 // slotted text layout"; wiretiles.hpp): object o's texts start toff[o]

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "b64.hpp"
+#include "bodyspans.hpp"
 #include "devio.hpp"
 #include "wiretiles.hpp"
 
@@ -105,6 +106,56 @@ __device__ __forceinline__ void slow_unit(const char* t, size_t unit, size_t nch
     atomicMin(bad, (unsigned long long)((size_t)(5 * j + k) * nchars + 16 * unit + fb));
 }
 
+// One fast-path unit of a text: its 16 characters as four dwords.  BODY (the
+// any-alignment form of k_acc_b64, include/amphora_client_bodies.h): the text
+// starts at ANY byte of a 16-byte aligned buffer.  Two fetches, A/B on one
+// MI355X at 4 Mi words x 3 parties (profiles/
+// clients_bodies.json; three party launches, K = 1 / 64 / 1,024):
+//   AMPH_BODY_FETCH = 1 (built): one 16-byte load at the text's own alignment,
+//     exactly the unit's bytes -- 0.646 / 0.646 / 0.670 ms;
+//   AMPH_BODY_FETCH = 0: the unit funnelled out of the one or two aligned
+//     16-byte granules bodyspans.hpp names for it -- two loads per lane, the
+//     second only when the unit straddles (its granule then holds the unit's
+//     own last characters, so no granule without text is read); the residue is
+//     the same for every unit of a text (workgroup-uniform), so the dword
+//     selection is a scalar branch and v_alignbyte does the remaining 0-3
+//     bytes -- 0.737 / 0.746 / 0.829 ms.
+// (One load per lane plus the neighbour's through a cross-lane move was not
+// built.)  Either way every byte read lies in a granule body_granules names.
+#ifndef AMPH_BODY_FETCH
+#define AMPH_BODY_FETCH 1
+#endif
+__device__ __forceinline__ uint4 funnel16(const uint4 lo, const uint4 hi, uint32_t residue) {
+  const uint32_t a = __builtin_amdgcn_readfirstlane(residue), b = a & 3u;
+  uint32_t s0, s1, s2, s3, s4;
+  switch (a >> 2) {
+    case 0: s0 = lo.x, s1 = lo.y, s2 = lo.z, s3 = lo.w, s4 = hi.x; break;
+    case 1: s0 = lo.y, s1 = lo.z, s2 = lo.w, s3 = hi.x, s4 = hi.y; break;
+    case 2: s0 = lo.z, s1 = lo.w, s2 = hi.x, s3 = hi.y, s4 = hi.z; break;
+    default: s0 = lo.w, s1 = hi.x, s2 = hi.y, s3 = hi.z, s4 = hi.w; break;
+  }
+  return make_uint4(__builtin_amdgcn_alignbyte(s1, s0, b), __builtin_amdgcn_alignbyte(s2, s1, b),
+                    __builtin_amdgcn_alignbyte(s3, s2, b), __builtin_amdgcn_alignbyte(s4, s3, b));
+}
+
+template <bool BODY>
+__device__ __forceinline__ uint4 text_unit(const char* t, size_t unit, size_t nchars) {
+  if constexpr (!BODY) {
+    return ld(reinterpret_cast<const uint4*>(t) + unit);
+  } else if constexpr (AMPH_BODY_FETCH == 1) {
+    typedef unsigned int bu32x4 __attribute__((ext_vector_type(4), aligned(1)));
+    const bu32x4 v = *reinterpret_cast<const bu32x4*>(t + 16 * unit);
+    return make_uint4(v.x, v.y, v.z, v.w);
+  } else {
+    const BodyUnit bu = body_unit((uint64_t)(uintptr_t)t, nchars, unit);
+    const uint4* g = reinterpret_cast<const uint4*>((uintptr_t)(bu.first << 4));
+    const uint4 lo = ld(g);
+    uint4 hi = lo;
+    if (bu.n == 2) hi = ld(g + 1);
+    return funnel16(lo, hi, bu.residue);
+  }
+}
+
 // toff: the texts start this many characters (a multiple of 16) into every
 // field buffer (the segmented kernels' slot offset).  MIXED (with FAST): the
 // tile that holds a text's end, lane by lane -- a lane whose unit ends at
@@ -112,8 +163,10 @@ __device__ __forceinline__ void slow_unit(const char* t, size_t unit, size_t nch
 // path does, a lane whose unit starts at or past nchars contributes zero
 // bits (what the per-character path decodes there) without decoding, and the
 // one or two lanes in between take the per-character path and read nothing
-// past the text.
-template <int NP, bool BIG, bool FAST, int BS, bool MIXED = false>
+// past the text.  BODY: text_unit's any-alignment fetch (the pointers of tx are
+// then the texts' own first bytes, toff 0); the per-character path reads byte
+// by byte at any address as it is.
+template <int NP, bool BIG, bool FAST, int BS, bool MIXED = false, bool BODY = false>
 __device__ __forceinline__ void wire_fields(const TextSet& tx, int n, size_t nchars, uint32_t pad,
                                             size_t words, uint4 (&raw)[5][NP > 0 ? NP : 1],
                                             uint32_t (*lds)[3 * BS], W4 (&acc)[5],
@@ -136,8 +189,7 @@ __device__ __forceinline__ void wire_fields(const TextSet& tx, int n, size_t nch
         if constexpr (kWirePrefetch > 0) {
           const int ahead = k * NP + j + kWirePrefetch;
           if (ahead < 5 * NP && (!MIXED || lane_fast))
-            raw[ahead / NP][ahead % NP] =
-                ld(reinterpret_cast<const uint4*>(tx.t[ahead / NP][ahead % NP] + toff) + unit);
+            raw[ahead / NP][ahead % NP] = text_unit<BODY>(tx.t[ahead / NP][ahead % NP] + toff, unit, nchars);
         }
         if (!MIXED || lane_fast) {
           uint32_t badb = 0;  // the per-unit branch also bounds the LDS reads' live ranges: one
@@ -150,7 +202,7 @@ __device__ __forceinline__ void wire_fields(const TextSet& tx, int n, size_t nch
         }
       } else if constexpr (FAST) {
         if (!MIXED || lane_fast) {
-          const uint4 v = ld(reinterpret_cast<const uint4*>(tx.t[k][j] + toff) + unit);
+          const uint4 v = text_unit<BODY>(tx.t[k][j] + toff, unit, nchars);
           uint32_t badb = 0;
           dec_unit16_lut(v, o, badb, lutp);
           if (badb & 0x80u) bad_unit(v, j, k, nchars, unit, bad);
@@ -189,9 +241,9 @@ __device__ __forceinline__ void wire_fields(const TextSet& tx, int n, size_t nch
   }
 }
 
-template <int NP, int BS>
+template <int NP, int BS, bool BODY = false>
 __device__ __forceinline__ void wire_load(const TextSet& tx, uint4 (&raw)[5][NP > 0 ? NP : 1], size_t tile,
-                                          size_t toff = 0, bool lane_fast = true) {
+                                          size_t toff = 0, bool lane_fast = true, size_t nchars = 0) {
   if constexpr (NP > 0) {
     const size_t unit = tile * BS + threadIdx.x;
 #pragma unroll
@@ -199,7 +251,7 @@ __device__ __forceinline__ void wire_load(const TextSet& tx, uint4 (&raw)[5][NP 
 #pragma unroll
       for (int j = 0; j < NP; ++j)
         if ((kWirePrefetch == 0 || k * NP + j < kWirePrefetch) && lane_fast)
-          raw[k][j] = ld(reinterpret_cast<const uint4*>(tx.t[k][j] + toff) + unit);
+          raw[k][j] = text_unit<BODY>(tx.t[k][j] + toff, unit, nchars);
   }
 }
 
@@ -441,20 +493,21 @@ __device__ __forceinline__ bool seg_tile(const uint64_t* woff, const uint64_t* t
   return true;
 }
 
-template <int NP, bool BIG, int BS>
+template <int NP, bool BIG, int BS, bool BODY = false>
 __device__ __forceinline__ void seg_fields(const TextSet& tx, int n, const SegTile& s,
                                            uint4 (&raw)[5][NP > 0 ? NP : 1], uint32_t (*lds)[3 * BS],
                                            W4 (&acc)[5], unsigned long long* bad, const Fp& f,
                                            const uint8_t* lutp) {
   const bool fast = (s.tile + 1) * Wire<BS>::chars + 4 <= s.nchars;
   if (fast) {
-    wire_load<NP, BS>(tx, raw, s.tile, s.toff);
-    wire_fields<NP, BIG, true, BS>(tx, n, s.nchars, s.pad, s.words, raw, lds, acc, bad, f, s.tile, lutp, s.toff);
+    wire_load<NP, BS, BODY>(tx, raw, s.tile, s.toff, true, s.nchars);
+    wire_fields<NP, BIG, true, BS, false, BODY>(tx, n, s.nchars, s.pad, s.words, raw, lds, acc, bad, f, s.tile, lutp,
+                                                s.toff);
   } else if constexpr (AMPH_WIRE_SEG_LANES) {
     const bool lane_fast = 16 * (s.tile * BS + threadIdx.x + 1) + 4 <= s.nchars;
-    wire_load<NP, BS>(tx, raw, s.tile, s.toff, lane_fast);
-    wire_fields<NP, BIG, true, BS, true>(tx, n, s.nchars, s.pad, s.words, raw, lds, acc, bad, f, s.tile, lutp,
-                                         s.toff, lane_fast);
+    wire_load<NP, BS, BODY>(tx, raw, s.tile, s.toff, lane_fast, s.nchars);
+    wire_fields<NP, BIG, true, BS, true, BODY>(tx, n, s.nchars, s.pad, s.words, raw, lds, acc, bad, f, s.tile, lutp,
+                                               s.toff, lane_fast);
   } else {
     wire_fields<NP, BIG, false, BS>(tx, n, s.nchars, s.pad, s.words, raw, lds, acc, bad, f, s.tile, lutp, s.toff);
   }
@@ -578,7 +631,18 @@ __global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_mask_json_seg(TextSet tx, 
 // words and take (5 party + field) * nchars_o + offset at [o].  The shape of
 // the launch is the kernel's one argument that differs between the forms, so
 // the one-secret form keeps its arguments and its code.
-template <bool SEG>
+//
+// BODY (with SEG; include/amphora_client_bodies.h): the K objects' texts lie
+// where the party's response bodies hold them.  All five text pointers are ONE
+// 16-byte aligned buffer (tx.t[0][0]) and object o's field k starts at byte
+// starts[k][o] of it, any residue mod 16 -- five scalar loads beside seg_tile's.
+// Fast lanes fetch through text_unit<true> (aligned granules, funnelled), the
+// last tile's per-character lanes read byte by byte as ever.  An object whose
+// first start is kBodyAbsent is a workgroup-uniform early exit: it reports
+// (5 party) * nchars_o -- what a slot of NUL bytes reports in the slotted form
+// -- and adds nothing to the sums.  Everything else is the SEG form's.
+constexpr uint64_t kBodyAbsent = ~(uint64_t)0;  // AMPH_BODY_ABSENT
+template <bool SEG, bool BODY = false>
 struct AccShape {  // one secret: its words, its text's characters and '=' padding
   size_t words, nchars;
   uint32_t pad;
@@ -588,15 +652,62 @@ struct AccShape<true> {  // the slotted layout's device tables
   const uint64_t *woff, *toff;
   size_t n_objects;
 };
+template <>
+struct AccShape<true, true> {  // the word table and starts[5][n_objects]
+  const uint64_t *woff, *starts;
+  size_t n_objects;
+};
 
-template <bool BIG, int BS, bool SEG>
-__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_acc_b64(TextSet tx, int party, AccShape<SEG> sh, SumSet sums,
+template <bool BIG, int BS, bool SEG, bool BODY = false>
+__global__ __launch_bounds__(BS) AMPH_WIRE_OCC void k_acc_b64(TextSet tx, int party, AccShape<SEG, BODY> sh, SumSet sums,
                                             unsigned long long* bad_session, unsigned long long* bad_call, Fp f) {
+  static_assert(SEG || !BODY, "the any-alignment form is a form of the K-secret kernel");
   __shared__ uint32_t lds[WireGroups<1>::bufs < 2 ? 2 : WireGroups<1>::bufs][3 * BS];
   __shared__ uint32_t lutw[kLutBytes / 4];
   __shared__ unsigned long long wg_bad;
   uint8_t* lutp = reinterpret_cast<uint8_t*>(lutw);
-  if constexpr (SEG) {
+  if constexpr (SEG && BODY) {
+    SegTile s;
+    // (field 0's starts stand where the slotted form's text offsets do: s.toff is starts[0][o])
+    const bool real = seg_tile<BS>(sh.woff, sh.starts, sh.n_objects, s);
+    uint64_t st[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 1; k < 5; ++k) st[k] = sh.starts[k * sh.n_objects + s.o];  // s.o < n_objects whatever the table holds
+    b64_lut_fill(lutp);
+    if (threadIdx.x == 0) wg_bad = ~0ULL;
+    __syncthreads();
+    if (!real) return;  // (the whole workgroup)
+    st[0] = s.toff;
+    if (st[0] == kBodyAbsent) {  // (the whole workgroup)
+      if (threadIdx.x == 0) {
+        const unsigned long long v = (unsigned long long)(5 * (size_t)party) * s.nchars;
+        atomicMin(bad_session + s.o, v);
+        if (bad_call) atomicMin(bad_call + s.o, v);
+      }
+      return;
+    }
+    TextSet bt;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) bt.t[k][0] = tx.t[0][0] + st[k];
+    s.toff = 0;
+    W4 acc[5];
+    uint4 raw[5][1];
+    seg_fields<1, BIG, BS, true>(bt, 1, s, raw, lds, acc, &wg_bad, f, lutp);
+    const size_t word = s.tile * Wire<BS>::words + threadIdx.x;
+    if (threadIdx.x < Wire<BS>::words && word < s.words) {  // s.w0 + s.words <= T: seg_tile's clamp
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        uint4* p = sums.s[k] + s.w0 + word;
+        *p = u4(mod_add(w4(*p), acc[k], f));
+      }
+    }
+    __syncthreads();  // every lane's report is in wg_bad
+    if (threadIdx.x == 0 && wg_bad != ~0ULL) {
+      const unsigned long long v = wg_bad + (unsigned long long)(5 * (size_t)party) * s.nchars;
+      atomicMin(bad_session + s.o, v);
+      if (bad_call) atomicMin(bad_call + s.o, v);
+    }
+  } else if constexpr (SEG) {
     SegTile s;
     const bool real = seg_tile<BS>(sh.woff, sh.toff, sh.n_objects, s);  // its table loads fly during the fill
     b64_lut_fill(lutp);
@@ -825,6 +936,23 @@ hipError_t launch_acc_b64_seg(const TextSet& tx, int party, const uint64_t* woff
     AMPH_LAUNCH((k_acc_b64<true, BS, true>), g, dim3(BS), c, tx, party, sh, sums, bad_session, bad_call, f);
   else
     AMPH_LAUNCH((k_acc_b64<false, BS, true>), g, dim3(BS), c, tx, party, sh, sums, bad_session, bad_call, f);
+  return hipGetLastError();
+}
+
+hipError_t launch_acc_b64_bodies(const char* buffer, int party, const uint64_t* woff, const uint64_t* starts,
+                                 size_t n_objects, size_t grid, const SumSet& sums, unsigned long long* bad_session,
+                                 unsigned long long* bad_call, const Fp& f, const LaunchCfg& c) {
+  if (grid == 0 || n_objects == 0) return hipSuccess;
+  if (grid > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  constexpr int BS = kWireBlock;
+  const dim3 g((unsigned)grid);
+  TextSet tx{};
+  tx.t[0][0] = buffer;
+  const AccShape<true, true> sh{woff, starts, n_objects};
+  if (f.big)
+    AMPH_LAUNCH((k_acc_b64<true, BS, true, true>), g, dim3(BS), c, tx, party, sh, sums, bad_session, bad_call, f);
+  else
+    AMPH_LAUNCH((k_acc_b64<false, BS, true, true>), g, dim3(BS), c, tx, party, sh, sums, bad_session, bad_call, f);
   return hipGetLastError();
 }
 

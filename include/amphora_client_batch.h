@@ -71,7 +71,8 @@
  * other objects are written either way.
  *
  * DEVICE MEMORY: 80 bytes per word of sums, 24 bytes per object of tables
- * and one verdict word per object, in ONE buffer taken from the context's
+ * (device mode: 40 more, the starts of amphora_client_bodies.h's calls) and
+ * one verdict word per object, in ONE buffer taken from the context's
  * pool of party-session buffers and handed back by amph_clients_free.  Host
  * mode moves a party's K texts of the five buffers as ONE page-locked image
  * and the finish call's secrets and outputs as one image each, through the
@@ -100,9 +101,10 @@
  *
  * OUT OF SCOPE: ragged parties (every party answers every object); a slot
  * handed in twice (resubmission); a fused "last party + finish" launch;
- * caller-chosen text offsets (the session fixes the dense layout); a C
- * gather form for host strings (the Python layer gathers); the C++ mirror,
- * JNI and Java bindings (none of the many-objects headers has them).
+ * caller-chosen text offsets in THESE calls (the slotted layout is fixed;
+ * amphora_client_bodies.h hands the same session a party's response bodies
+ * as they lie, every text at its own byte); the C++ mirror, JNI and Java
+ * bindings (none of the many-objects headers has them).
  */
 #ifndef AMPHORA_CLIENT_BATCH_H_
 #define AMPHORA_CLIENT_BATCH_H_

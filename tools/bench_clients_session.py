@@ -26,6 +26,26 @@ medians over --reps repetitions after --warmup, with min and max.  The outputs
 of the three forms are compared byte for byte before anything is timed.
 Launch counts come from amph_ctx_stats, copies from amph_clients_copies.
 Prints one JSON line; --out also writes it to a file.
+
+--bodies (include/amphora_client_bodies.h): instead of the above, every party's
+K responses as K JSON bodies with the five members inside, and three pairs of
+forms on the same texts, alternating inside each repetition:
+
+  device   the N accumulate launches of a device-mode session: amph_clients_party_dev
+           on the slotted buffers against amph_bodies_party_dev on ONE device buffer
+           that holds the bodies (its starts upload included); HIP events.  Run
+           under rocprofv3 --kernel-trace --stats this gives the two kernel forms.
+  host     amph_clients_party on the (already gathered) slotted buffers against
+           amph_bodies_party on the K bodies, per party call; host clock
+  python   ResponseSessions.add_bodies for all parties, in_place=True against
+           in_place=False (the scan in C and no gather, against
+           wire.odo_field_texts and the per-object, per-field gather); host clock
+
+The secrets of the two forms of each pair are compared before anything is timed.
+--variant-lib LIB adds the device pair a third form, "bodies_variant": the same
+calls through a second library built from the same tree with another fetch
+(-DAMPH_BODY_FETCH=1: one unaligned 16-byte load per lane and field instead of
+two aligned ones and the funnel).
 """
 import argparse
 import ctypes as C
@@ -50,6 +70,10 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--modes", default="host,device")
 ap.add_argument("--out", default=None)
+ap.add_argument("--bodies", action="store_true", help="the body calls against the slotted calls")
+ap.add_argument("--variant-lib", default=None,
+                help="--bodies, device mode: a library built with -DAMPH_BODY_FETCH=1 (tools/build_native.py "
+                     "build_variant): its amph_bodies_party_dev as a third form, in the same process")
 a = ap.parse_args()
 T, n = a.words, a.parties
 if not torch.cuda.is_available():
@@ -272,6 +296,179 @@ def run_mode(S, dev, mask):
     res["total_over_loop"] = round(res["session"]["total"]["median_ms"] / res["loop_of_single_sessions"]["median_ms"], 4)
     return res
 
+
+def bodies_of(S):
+    """Per party the K response bodies (bytes) cut from the host slotted
+    buffers, and their (K, 5) member starts (amph_bodies_scan)."""
+    host = S.bufs(False)
+    head = b'{"secretId":"00000000-0000-0000-0000-00000000002a","tags":[{"key":"k","value":"v","valueType":"STRING"}]'
+    bodies, starts = [], []
+    for j in range(n):
+        bs, st = [], np.empty((S.K, 5), np.uint64)
+        for o in range(S.K):
+            a0, nc = int(S.foff[o]), S.nc[o]
+            bs.append(head + b"".join(b',"%s":"' % name.encode() + host[j][k][a0:a0 + nc].tobytes() + b'"'
+                                      for k, name in enumerate(LIB.ODO_FIELD_NAMES)) + b"}")
+            st[o], lens = LIB.bodies_scan(bs[-1])
+            assert (lens == nc).all()
+        bodies.append(bs)
+        starts.append(st)
+    return bodies, starts
+
+
+def run_bodies(S):
+    from amphora_amd import client
+    K = S.K
+    bodies, starts = bodies_of(S)
+    host = S.bufs(False)
+    out = {"body_bytes_per_party": sum(len(b) for b in bodies[0]), "slotted_bytes_per_party": 5 * S.field_chars}
+
+    def finish(s):
+        y = s.finish_verify()[0]
+        if s.dev:
+            torch.cuda.synchronize()
+        return y.cpu().numpy() if s.dev else y
+
+    V = vctx = None
+    if a.variant_lib and "device" in a.modes.split(","):
+        V = C.CDLL(os.path.abspath(a.variant_lib))
+        vp = C.c_void_p
+        V.amph_ctx_create.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp)]
+        V.amph_clients_begin_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.POINTER(vp)]
+        V.amph_bodies_party_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp]
+        V.amph_clients_finish_verify_dev.argtypes = [vp, vp, vp, vp, vp]
+        V.amph_clients_free.argtypes = [vp]
+        V.amph_clients_free.restype = None
+        V.amph_last_error.restype = C.c_char_p
+        vctx = vp()
+        keys = [LIB.le16(x) for x in (TEST_PRIME, TEST_R, TEST_RINV)]
+        if V.amph_ctx_create(*keys, 0, C.byref(vctx)) != 0:
+            raise RuntimeError("variant context: %s" % V.amph_last_error().decode())
+
+    def variant(check=False):
+        """The N amph_bodies_party_dev calls through the variant library."""
+        def vok(st):
+            if st != 0:
+                raise RuntimeError("variant status %d: %s" % (st, V.amph_last_error().decode()))
+        h, sp = C.c_void_p(), C.c_void_p(stream.cuda_stream)
+        vok(V.amph_clients_begin_dev(vctx, S.woff.ctypes.data, K, n, sp, C.byref(h)))
+        ev[0].record(stream)
+        for j in range(n):
+            vok(V.amph_bodies_party_dev(h, j, dbufs[j].data_ptr(), dbufs[j].numel(), absolute[j].ctypes.data, sp))
+        ev[1].record(stream)
+        y = None
+        if check:
+            y = torch.zeros((T, 16), dtype=torch.uint8, device="cuda")
+            ff, bad = (torch.zeros(K, dtype=torch.int64, device="cuda") for _ in range(2))
+            torch.cuda.synchronize()
+            vok(V.amph_clients_finish_verify_dev(h, y.data_ptr(), ff.data_ptr(), bad.data_ptr(), sp))
+        V.amph_clients_free(h)  # waits for the stream
+        stream.synchronize()
+        return [ev[0].elapsed_time(ev[1])], (y.cpu().numpy() if check else None)
+
+    for mode in a.modes.split(","):
+        dev = mode == "device"
+        if dev:
+            stream = torch.cuda.Stream()
+            at = np.concatenate([[0], np.cumsum([(len(b) + 15) & ~15 for b in bodies[0]])]).astype(np.uint64)
+            dbufs, absolute = [], []
+            for j in range(n):
+                buf = np.zeros(int(at[-1]) + 16, np.uint8)
+                for b, x in zip(bodies[j], at):
+                    buf[int(x):int(x) + len(b)] = np.frombuffer(b, np.uint8)
+                dbufs.append(torch.from_numpy(buf).cuda())
+                absolute.append(starts[j] + at[:-1, None])
+            torch.cuda.synchronize()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+        def one(form, check=False):
+            """-> ms of the N party calls (device: events around them; host: per call, summed)."""
+            s = ctx.clients_begin_dev(S.woff, n, stream) if dev else ctx.clients_begin(S.woff, n)
+            per = []
+            with s:
+                if dev:
+                    ev[0].record(stream)
+                for j in range(n):
+                    t0 = time.perf_counter()
+                    if form == "slotted":
+                        s.party(j, S.dev[j] if dev else host[j])
+                    elif dev:
+                        s.party_bodies_dev(j, dbufs[j], absolute[j])
+                    else:
+                        s.party_bodies(j, bodies[j], starts[j])
+                    per.append(1e3 * (time.perf_counter() - t0))
+                if dev:
+                    ev[1].record(stream)
+                    stream.synchronize()
+                    per = [ev[0].elapsed_time(ev[1])]
+                y = finish(s) if check else None
+                if dev:
+                    torch.cuda.synchronize()
+            return per, y
+
+        (_, y0), (_, y1) = one("slotted", True), one("bodies", True)
+        if not np.array_equal(y0, y1):
+            raise RuntimeError("K=%d %s: the body form's secrets differ from the slotted form's" % (K, mode))
+        rows = {"slotted": [], "bodies": []}
+        if dev and V is not None:
+            rows["bodies_variant"] = []
+            if not np.array_equal(y0, variant(True)[1]):
+                raise RuntimeError("K=%d: the variant library's secrets differ from the slotted form's" % K)
+        for rep in range(a.warmup + a.reps):
+            for form in rows:
+                per, _ = variant() if form == "bodies_variant" else one(form)
+                if rep >= a.warmup:
+                    rows[form].append(per)
+        res = {form: {"parties_total": spread([sum(p) for p in rows[form]]),
+                      "party_ms": [med([p[j] for p in rows[form]]) for j in range(len(rows[form][0]))]}
+               for form in rows}
+        res["bodies_over_slotted"] = round(res["bodies"]["parties_total"]["median_ms"] /
+                                           res["slotted"]["parties_total"]["median_ms"], 4)
+        if "bodies_variant" in res:
+            res["variant_over_bodies"] = round(res["bodies_variant"]["parties_total"]["median_ms"] /
+                                               res["bodies"]["parties_total"]["median_ms"], 4)
+        out[mode] = res
+    if "host" in a.modes.split(","):
+        util = client.SecretShareUtil(ctx)
+        texts = [[b.decode("ascii") for b in bs] for bs in bodies]
+        rows = {True: [], False: []}
+        for rep in range(a.warmup + a.reps):
+            for in_place in (True, False):
+                with client.ResponseSessions(util, n, in_place=in_place) as rs:
+                    t0 = time.perf_counter()
+                    for j in range(n):
+                        rs.add_bodies(j, texts[j])
+                    t1 = time.perf_counter()
+                    if rep == 0:  # the same secrets either way
+                        got = rs.secrets()
+                        if any(isinstance(g, Exception) for g in got):
+                            raise RuntimeError("K=%d add_bodies(in_place=%s): %r" % (K, in_place, got[0]))
+                        rows.setdefault("y", []).append([g[2] for g in got] if K <= 64 else None)
+                if rep >= a.warmup:
+                    rows[in_place].append(1e3 * (t1 - t0))
+        if rows["y"][0] != rows["y"][1]:
+            raise RuntimeError("K=%d: add_bodies in place and gathered give different secrets" % K)
+        out["python_add_bodies"] = {"in_place": spread(rows[True]), "gather": spread(rows[False]),
+                                    "in_place_over_gather": round(med(rows[True]) / med(rows[False]), 4)}
+    return out
+
+
+if a.bodies:
+    res = {"tool": "bench_clients_session --bodies", "device": torch.cuda.get_device_name(0), "words_total": T,
+           "parties": n, "reps": a.reps, "warmup": a.warmup, "host_memory": "pageable",
+           "timing": {"host": "host clock around calls that end in a device synchronisation",
+                      "device": "device time between HIP events around the N party calls on one stream"},
+           "objects": {}}
+    for K in [int(x) for x in a.objects.split(",")]:
+        S = Setup(K)
+        res["objects"][str(K)] = dict(run_bodies(S), words_per_object=S.sizes[0])
+        del S
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    sys.exit(0)
 
 res = {"tool": "bench_clients_session", "device": torch.cuda.get_device_name(0), "words_total": T, "parties": n,
        "reps": a.reps, "warmup": a.warmup, "host_memory": "pageable",
